@@ -25,6 +25,14 @@ Roofline: the dominant kernel of the step (by its HIP-event time) against HBM
 peak with compulsory bytes, plus the counter-derived DRAM bytes
 (FETCH_SIZE x2 on gfx950 + WRITE_SIZE) and VALU issue fraction of the same
 kernel from the committed PMC summary (profiles/r03_pmc_config<N>.json, else r02).
+
+A plain run sets up, warms up, times the K steps and prints the result line with
+the headline figure (value, ms_per_step) and what the timed steps themselves
+report. Everything that takes runs of its own comes with --full only: the serial
+run and its per-stage times, the per-kernel profile and rooflines, the oracle
+parity check, the end-to-end (pack + upload + schedule) figures and the CPU
+baseline. --dump-outputs DIR writes the CSR results of the last timed step as
+DIR/<name>.npy (dump_outputs below), in either mode.
 """
 import argparse
 import ctypes as C
@@ -212,6 +220,58 @@ def parity_check(u, results, opts, n_check, seed):
     return n, bad
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of array data --dump-outputs may write
+DUMP_SEED = 20240607           # fixes which bindings a sampled dump keeps
+
+
+def dump_outputs(path, csr, suffix=""):
+    """--dump-outputs: the CSR results of one step (what kp_schedule_batch hands its
+    caller) as <path>/<name><suffix>.npy: status, err_code, err_arg per binding, offsets
+    (n + 1), cluster_idx and replicas per target, each binding's targets in cluster order
+    (below). Every value is an integer, stored as
+    float32 where the array's values are below 2^24 (exact) and as float64 otherwise.
+    If the whole result exceeds DUMP_BUDGET, a fixed seeded sample of the bindings is
+    kept (in binding order, offsets rebased to the kept targets) and binding_index
+    names them. Returns a short description for the result line."""
+    import numpy as np
+
+    def flt(a):
+        a = np.asarray(a)
+        small = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+        return a.astype(np.float32 if small else np.float64)
+    n = csr.n_bindings
+    # A binding's targets are a set: the engine emits them in whatever order its lanes
+    # finish, which differs from run to run (the parity checks compare them as multisets,
+    # as the reference's IsScheduleResultEqual does). Written in cluster order within each
+    # binding, equal results give equal files.
+    owner = np.repeat(np.arange(n), np.diff(csr.offsets))
+    order = np.lexsort((csr.replicas, csr.cluster_idx, owner))
+    arrays = {"status": flt(csr.status), "err_code": flt(csr.err_code), "err_arg": flt(csr.err_arg),
+              "offsets": flt(csr.offsets), "cluster_idx": flt(csr.cluster_idx[order]),
+              "replicas": flt(csr.replicas[order])}
+    kept = n
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        counts = np.diff(csr.offsets)
+        per_bind = sum(arrays[k].itemsize for k in ("status", "err_code", "err_arg", "offsets")) + 8
+        per_targ = arrays["cluster_idx"].itemsize + arrays["replicas"].itemsize
+        perm = np.random.default_rng(DUMP_SEED).permutation(n)
+        cum = np.cumsum(per_bind + per_targ * counts[perm])
+        kept = int(np.searchsorted(cum, DUMP_BUDGET - 64, side="right"))
+        idx = np.sort(perm[:kept])
+        offs = np.concatenate(([0], np.cumsum(counts[idx])))
+        # target t of kept binding j sits at offsets[idx[j]] + (t - offs[j]) in the whole result
+        tsel = np.repeat(csr.offsets[idx] - offs[:-1], counts[idx]) + np.arange(offs[-1])
+        arrays = {"binding_index": idx.astype(np.float64), "status": arrays["status"][idx],
+                  "err_code": arrays["err_code"][idx], "err_arg": arrays["err_arg"][idx],
+                  "offsets": offs.astype(arrays["offsets"].dtype), "cluster_idx": arrays["cluster_idx"][tsel],
+                  "replicas": arrays["replicas"][tsel]}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+    return {"dir": path, "arrays": sorted(arrays), "bindings": kept, "of": n,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` without WORLD_SIZE: start N rank processes of this script
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run sets them,
@@ -251,11 +311,19 @@ def main():
     ap.add_argument("--clusters", type=int, default=None)
     ap.add_argument("--bindings", type=int, default=None, help="bindings per GPU")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what has runs of its own: the serial run and per-stage "
+                         "times, the per-kernel profile and rooflines, the oracle parity check (--check), the "
+                         "end-to-end figures (--e2e-reps) and the CPU baseline (--no-cpu: without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (CSR arrays) as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--check", type=int, default=1000,
-                    help="bindings of the timed batch re-checked against the oracle after timing (0: off)")
-    ap.add_argument("--e2e-reps", type=int, default=5, help="timed pack+upload+schedule repetitions (0: off)")
+                    help="with --full: bindings of the timed batch re-checked against the oracle after timing "
+                         "(0: off)")
+    ap.add_argument("--e2e-reps", type=int, default=5,
+                    help="with --full: timed pack+upload+schedule repetitions (0: off)")
     ap.add_argument("--e2e-churn", type=float, default=0.1,
                     help="share of bindings at a new generation per end-to-end cycle (the rest reuse their records)")
     ap.add_argument("--lib", default=None, help="engine library (default karmada_amd/libkp.so)")
@@ -408,6 +476,7 @@ def main():
                     clock["t0"] = now
                 elif d == n_warm + args.steps:
                     clock["t1"] = now
+                    clock["last_lane"] = k  # (this lane issues nothing more: its result stays)
                 timed = n_warm < d <= n_warm + args.steps
             results[k] = r
             if timed:
@@ -439,6 +508,101 @@ def main():
     lanes_wall = time.perf_counter() - t_start
     elapsed = clock["t1"] - clock["t0"]
     rank_ms = 1e3 * elapsed / args.steps
+    # the last timed step's results (the lane that completed it issued nothing after it)
+    out_csr = Csr.from_results(results[clock["last_lane"]])
+    dump_suffix = f".rank{rank}" if world > 1 else ""
+
+    def headline(elapsed, per_rank_ms, n_ok, n_targets, last):
+        """The result line's fields that the timed steps alone give (both modes)."""
+        bits = last["bits"] == 1
+        return {
+            "metric": "ResourceBindings scheduled/sec at 100k bindings x 5k clusters",
+            # every rank's bindings over the max-over-ranks time of one step
+            "value": round(total / (elapsed / args.steps), 1),
+            "unit": "ResourceBindings/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "full": args.full,
+            "inflight": len(lanes),
+            "batches_per_lane": per_lane,
+            # the hardware-queue count requested of the HIP runtime (GPU_MAX_HW_QUEUES; unset:
+            # HIP's default 4) and the streams each engine drives
+            "hip_hw_queues_requested": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+            "streams_per_engine": int(os.environ.get("KP_STREAMS", "3")),
+            "host_wait": "blocking" if os.environ.get("KP_SYNC_BLOCK", "0") not in ("", "0") else "polling",
+            # the timed window: from the (warmup x inflight)-th completed step to the K-th
+            # completion after it, every lane mid-stream (module docstring)
+            "timed_window": {"warmup_completions": n_warm, "timed_completions": args.steps,
+                             # gaps between consecutive completions in the window (ms, lane): a
+                             # stall shows as one long gap, a uniformly slow run as even ones
+                             "gaps_ms": timed_gaps(clock, n_warm, args.steps),
+                             "total_completions": clock["done"],
+                             "lanes_wall_s": round(lanes_wall, 3)},
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int64",
+            "data": "synthetic",
+            "config": {"workload": f"config{cfg}: {B} bindings/GPU x {C_} clusters, seed {seed}, "
+                                   "resource-model grades, DynamicWeight/Aggregated" if cfg == 3 else
+                       f"config{cfg}: {B} bindings/GPU x {C_} clusters, seed {seed}",
+                       "bindings_per_gpu": B, "bindings_total": total, "clusters": C_,
+                       "parallelism": f"binding-shard x{world}" + (" (cost-balanced, RCCL snapshot broadcast + "
+                                                                   "CSR all-gather)" if world > 1 else "")},
+            "filter_mode": "bitset filter + estimator classes" if bits else "per-binding pair rows",
+            "estimator_classes": int(last["n_classes"]) if bits else None,
+            "setup_s": {"generate": round(gen_s, 2), "snapshot_pack_upload": round(snap_s, 3),
+                        "binding_pack_upload": round(pack_s, 3)},
+            "per_rank_ms": per_rank_ms,
+            "scheduled_ok": n_ok,
+            "result_targets": n_targets,
+            "slow_path_bindings": int(last["n_slow"]),
+            # SEL_ALL DynamicWeight/Aggregated bindings scheduled over their deciding candidates
+            # (k_select_top) and the ones it handed to the full-candidate kernel
+            "select_top": {"bindings": int(last["n_top"]), "fallback": int(last["n_top_fallback"])},
+            # cluster-spread bindings, and those selected over their estimator-class order
+            "select_cluster": {"bindings": int(last["n_cluster"]), "class_order": int(last["n_cluster_order"])},
+            "select_region": {"bindings": int(last["n_region"]), "class_order": int(last["n_region_order"])},
+        }
+
+    if not args.full:
+        # a plain run ends here: the headline figure, the last timed step's own counters
+        # and (--dump-outputs) its results; nothing else is run
+        for e_k, s_k, b_k, b_k2 in lanes[1:]:
+            b_k.close()
+            if b_k2 is not None:
+                b_k2.close()
+            s_k.close()
+            e_k.close()
+        if lanes[0][3] is not None:
+            lanes[0][3].close()
+        batch.close()
+        n_ok, n_targets = int((out_csr.status == 0).sum()), out_csr.n_targets
+        per_rank_ms = [round(rank_ms, 3)]
+        if dist is not None:
+            import torch
+            t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+            pr = [torch.zeros(1, dtype=torch.float64, device=tdev) for _ in range(dist.get_world_size())]
+            dist.all_gather(pr, torch.tensor([rank_ms], dtype=torch.float64, device=tdev))
+            per_rank_ms = [round(float(x.item()), 3) for x in pr]
+            t = torch.tensor([n_ok, n_targets], dtype=torch.int64, device=tdev)
+            dist.all_reduce(t)
+            n_ok, n_targets = int(t[0].item()), int(t[1].item())
+        line = headline(elapsed, per_rank_ms, n_ok, n_targets, st_all[-1])
+        if args.dump_outputs:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, out_csr, dump_suffix)
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        snap.close()
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # every lane's last result (engine-owned until that engine's next call), copied
     # now: the in-flight lanes are parity-checked too, not only the serial run below
     lane_csr = [Csr.from_results(x) for x in results if x is not None]
@@ -649,43 +813,11 @@ def main():
             "dram_frac": pmc_frac("hbm_bytes", HBM_PEAK_GBS), "valu_frac": pmc_frac("valu_insts", VALU_PEAK_GINST)}
     step_bytes = pair_b + sel_b
     step_gbs = step_bytes / (ms_per_step * 1e-3) / 1e9
-    line = {
-        "metric": "ResourceBindings scheduled/sec at 100k bindings x 5k clusters",
-        "value": round(value, 1),
-        "unit": "ResourceBindings/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "inflight": len(lanes),
-        "batches_per_lane": per_lane,
-        # the hardware-queue count requested of the HIP runtime (GPU_MAX_HW_QUEUES; unset:
-        # HIP's default 4) and the streams each engine drives
-        "hip_hw_queues_requested": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-        "streams_per_engine": int(os.environ.get("KP_STREAMS", "3")),
-        "host_wait": "blocking" if os.environ.get("KP_SYNC_BLOCK", "0") not in ("", "0") else "polling",
-        # the timed window: from the (warmup x inflight)-th completed step to the K-th
-        # completion after it, every lane mid-stream (module docstring)
-        "timed_window": {"warmup_completions": n_warm, "timed_completions": args.steps,
-                         # gaps between consecutive completions in the window (ms, lane): a
-                         # stall shows as one long gap, a uniformly slow run as even ones
-                         "gaps_ms": timed_gaps(clock, n_warm, args.steps),
-                         "total_completions": clock["done"],
-                         "lanes_wall_s": round(lanes_wall, 3)},
+    line = headline(elapsed, per_rank_ms, n_ok, n_targets, last)
+    line.update({
         # one batch at a time on one engine (nothing overlapped): ms per batch and the rate
         "serial_ms_per_step": round(serial_ms, 3) if serial_ms else round(ms_per_step, 3),
         "serial_value": round(total / (serial_ms * 1e-3), 1) if serial_ms else round(value, 1),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic",
-        "config": {"workload": f"config{cfg}: {B} bindings/GPU x {C_} clusters, seed {seed}, "
-                               "resource-model grades, DynamicWeight/Aggregated" if cfg == 3 else
-                   f"config{cfg}: {B} bindings/GPU x {C_} clusters, seed {seed}",
-                   "bindings_per_gpu": B, "bindings_total": total, "clusters": C_,
-                   "parallelism": f"binding-shard x{world}" + (" (cost-balanced, RCCL snapshot broadcast + "
-                                                               "CSR all-gather)" if world > 1 else "")},
         "roofline": roof,
         # every kernel of one step (serial, profiled): HIP-event ms, launches, bindings (or
         # class rows) covered, compulsory bytes and the rate they imply, slowest first
@@ -699,8 +831,6 @@ def main():
                       "select_top_kernel": round(top_ms, 3), "select_cluster_kernel": round(avg("cluster_kernel_ms"), 3),
                       "host_region": round(avg("host_ms"), 3), "copy_back": round(avg("copy_ms"), 3),
                       "call_total": round(avg("total_ms"), 3)},
-        "filter_mode": "bitset filter + estimator classes" if bits else "per-binding pair rows",
-        "estimator_classes": int(last["n_classes"]) if bits else None,
         # bindings/s including host packing + upload, pipelined over two engines (every
         # binding packed anew), and one batch at a time (end_to_end_serial_ms per batch);
         # reuse: the same pipeline re-scheduling each batch with `churn` of its bindings at a
@@ -711,25 +841,15 @@ def main():
         "end_to_end_reuse": {"value": round(total / e2e_reuse, 1) if e2e_reuse else None,
                              "ms": round(1e3 * e2e_reuse, 2) if e2e_reuse else None,
                              "churn": args.e2e_churn, "records_reused": round(reuse_hits, 4)},
-        "setup_s": {"generate": round(gen_s, 2), "snapshot_pack_upload": round(snap_s, 3),
-                    "binding_pack_upload": round(pack_s, 3)},
-        "per_rank_ms": per_rank_ms,
-        "scheduled_ok": n_ok,
-        "result_targets": n_targets,
-        "slow_path_bindings": int(last["n_slow"]),
-        # SEL_ALL DynamicWeight/Aggregated bindings scheduled over their deciding candidates
-        # (k_select_top) and the ones it handed to the full-candidate kernel
-        "select_top": {"bindings": int(last["n_top"]), "fallback": int(last["n_top_fallback"])},
-        # cluster-spread bindings, and those selected over their estimator-class order
-        "select_cluster": {"bindings": int(last["n_cluster"]), "class_order": int(last["n_cluster_order"])},
-        "select_region": {"bindings": int(last["n_region"]), "class_order": int(last["n_region_order"])},
         # bindings of the timed batch (sampled over all ranks) re-checked against the oracle
         "parity_checked": n_chk,
         "parity_lanes": n_lanes_chk,  # result lists checked per rank: the serial run + each in-flight lane
         "parity_bad": n_bad,
         "parity_source": "all-gathered CSR (each rank's range) + every in-flight lane" if dist is not None else
                          "serial run + every in-flight lane",
-    }
+    })
+    if args.dump_outputs:
+        line["dump_outputs"] = dump_outputs(args.dump_outputs, out_csr, dump_suffix)
     if rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(u, opts, args.cpu_budget)
     if rank == 0:

@@ -35,7 +35,7 @@ def run_world1(args, env_extra, timeout):
 
 
 def test_world1_gloo_cpusim():
-    line = run_world1(["--config", "6", "--bindings", "300", "--steps", "2", "--warmup", "1", "--check", "300",
+    line = run_world1(["--full", "--config", "6", "--bindings", "300", "--steps", "2", "--warmup", "1", "--check", "300",
                        "--no-cpu", "--e2e-reps", "0", "--inflight", "2", "--lib", "karmada_amd/libkp_cpusim.so"],
                       {"KP_DIST_BACKEND": "gloo", "KP_CPUSIM_THREADS": "2"}, 300)
     assert line["parity_source"].startswith("all-gathered CSR")
@@ -47,7 +47,7 @@ def test_world1_gloo_cpusim():
 def test_world1_rccl_config5():
     """Config 5 (C = 10 000, the mix of configs 2-4) over RCCL at world size 1: the
     gathered CSR of 2 000 bindings equals the oracle's placements."""
-    line = run_world1(["--config", "5", "--bindings", "2000", "--steps", "2", "--warmup", "1", "--check", "2000",
+    line = run_world1(["--full", "--config", "5", "--bindings", "2000", "--steps", "2", "--warmup", "1", "--check", "2000",
                        "--no-cpu", "--e2e-reps", "0", "--inflight", "2"], {"KP_DIST_BACKEND": "nccl"}, 600)
     assert line["parity_source"].startswith("all-gathered CSR")
     assert line["parity_checked"] == 2000 and line["parity_bad"] == 0

@@ -1,5 +1,6 @@
-"""Summary of bench.py JSON lines: python tools/gpu/summ.py file... (rate, step, serial, e2e,
-parity, the five slowest kernels, every launch with 0 units)."""
+"""Summary of `bench.py --full` JSON lines: python tools/gpu/summ.py file... (rate, step, serial,
+e2e, parity, the five slowest kernels, every launch with 0 units; a plain run's line has the
+rate and step only)."""
 import json
 import sys
 for f in sys.argv[1:]:
