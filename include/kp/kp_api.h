@@ -301,7 +301,9 @@ enum {
 
 /* The reference error site that produced a non-OK status. */
 enum {
-  KP_ERR_NONE = 0,
+  KP_ERR_NONE = 0,                   /* with KP_STATUS_ERROR: a request the packer rejected (never the select
+                                        paths: a region spread selects any number of clusters up to the
+                                        snapshot's, and spec.Clusters may repeat names at any length) */
   KP_ERR_FIT = 1,                    /* generic_scheduler.go:84-89; arg = NumAllClusters */
   KP_ERR_REGION_MIN_GROUPS = 2,      /* select_clusters_by_region.go:30-32 */
   KP_ERR_REGION_CLUSTER_MIN = 3,     /* select_clusters_by_region.go:37-39 */
@@ -386,6 +388,8 @@ typedef struct kp_stage_times {
   float cluster_kernel_ms;  /* the cluster-spread select kernel alone (HIP events on its stream) */
   uint32_t n_region;        /* region-spread bindings (selectBestClustersByRegion) */
   uint32_t n_region_order;  /* of those, the ones whose final selection walked their estimator-class order */
+  uint32_t n_region_wide;   /* of those, the ones k_region_wide scheduled or errored: a selection of more than
+                               256 clusters, or a repeated spec.Clusters of more than 256 entries */
 } kp_stage_times;
 
 /* ------------------------------------------------------------------------- */

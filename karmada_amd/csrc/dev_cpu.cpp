@@ -211,6 +211,16 @@ int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const Sele
   return 0;
 }
 
+int region_wide(stream_t, const KArgs& a, const SelectExtra& x, const int32_t* wide, int n_wide,
+                unsigned char* scratch, size_t slot_bytes, int g, int cap, int lds_sort, uint32_t* n_done) {
+  if (n_wide <= 0 || g <= 0) return 0;
+  grid(g, region_wide_lds_bytes(a.s.Cp, a.s.n_regions, lds_sort), [&](int blk, unsigned char* sm) {
+    body_region_wide(CpuBlk{(int64_t*)sm}, blk, g, sm, a, wide, n_wide, x.rsel, x.rnsel, scratch, slot_bytes, cap,
+                     lds_sort, n_done);
+  });
+  return 0;
+}
+
 int class_order(stream_t, const SnapView& s, const int32_t* rows, int n_rows, uint64_t* ord, int64_t* tot,
                 int32_t* ok) {
   int P = 1;

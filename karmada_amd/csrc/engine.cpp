@@ -445,6 +445,7 @@ struct kp_batch {
                               // fallbacks, [10] / [11] cluster- / region-spread bindings selected over the class order,
                               // [12] / [13] k_spread_order's fallback list lengths, [14] k_region_a_order's
                               // [16] k_select_top's capacity overflows (the top_cap_mid launch)
+                              // [17] bindings k_region_wide scheduled or errored
   uint32_t* out_idx = nullptr;
   int32_t* out_rep = nullptr;
   uint64_t* offsets_d = nullptr;
@@ -457,6 +458,15 @@ struct kp_batch {
   unsigned char* slow_scratch = nullptr;
   size_t slow_slot = 0;
   int slow_grid = 0, slow_cap = 0, slow_lds = 0, slow_sort = 0;
+  // k_region_wide: the rows of l_region whose selection can outgrow k_region_b's lists
+  // (cluster MaxGroups > kSmallMax, or a repeated spec.Clusters past kTgtSmallMax), its
+  // own scratch slots (k_slow may run beside it) and LDS sort area; all empty / 0 for a
+  // batch without such bindings, which then launches and allocates nothing for it
+  std::vector<int32_t> l_region_wide;
+  int32_t* d_region_wide = nullptr;
+  unsigned char* wide_scratch = nullptr;
+  size_t wide_slot = 0;
+  int wide_grid = 0, wide_sort = 0;
   bool fast_ok = false;  // the batch half of the fast pair-kernel condition (batch_fast_ok)
   int n_regions = 0;     // the snapshot's region count the region buffers were sized for
   // host results
@@ -1921,6 +1931,8 @@ int batch_lds_check(kp_engine* e, const kp_snapshot* s, const kp_batch* bt) {
   if (!bt->l_all.empty()) need = std::max(need, smem_all(s));
   if (!bt->l_cluster.empty()) need = std::max(need, smem_cluster(s, cap));
   if (!bt->l_region.empty()) need = std::max({need, smem_region_a(s), smem_region_b(s, cap)});
+  if (!bt->l_region_wide.empty())
+    need = std::max(need, region_wide_lds_bytes(s->Cp, s->view.n_regions, bt->wide_sort));
   if (need > e->max_lds) {
     e->err = "snapshot too large for one workgroup's LDS (" + std::to_string(need) + " > " +
              std::to_string(e->max_lds) + " bytes)";
@@ -3199,6 +3211,22 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     e->err = "region spread over more than 256 regions is not supported";
     return KP_ENOTSUP;
   }
+  // the region bindings that can need k_region_wide, by their row in l_region (rsel, rnsel
+  // and rout are indexed by it)
+  for (size_t j = 0; j < bt->l_region.size(); j++) {
+    const BindHdr& h = bt->hdr[bt->l_region[j]];
+    if (h.cluster_max > kSmallMax || ((h.flags & BF_DUP_TARGETS) && h.tgt_cnt > kTgtSmallMax))
+      bt->l_region_wide.push_back((int32_t)j);
+  }
+  if (!bt->l_region_wide.empty()) {
+    // its candidate sort in LDS when the keys fit beside the rest (KP_WIDE_LDS=0, a
+    // diagnostic, keeps them in the global slot), as k_slow's
+    int P = 1;
+    while (P < s->Cp) P <<= 1;
+    const char* g = getenv("KP_WIDE_LDS");
+    if (!(g && g[0] == '0') && region_wide_lds_bytes(s->Cp, s->view.n_regions, 8 * P) <= e->max_lds)
+      bt->wide_sort = 8 * P;
+  }
   if (batch_lds_check(e, s, bt)) return KP_ENOTSUP;
   bt->n_regions = s->view.n_regions;
   auto pad1 = [](auto& v) {
@@ -3237,6 +3265,13 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   // keys and scale-down scratch in the global slot (no LDS sort, no wave sort.Sort)
   if (const char* g = getenv("KP_SLOW_GRID")) bt->slow_grid = std::max(1, std::min(bt->slow_grid, atoi(g)));
   if (const char* g = getenv("KP_SLOW_LDS"); g && g[0] == '0') bt->slow_sort = bt->slow_lds = 0;
+  if (!bt->l_region_wide.empty()) {
+    // one slot per workgroup; the grid capped so the slots stay within 256 MB (a slot is
+    // ~37 MB at Cp = 262144, ~0.8 MB at C = 5000)
+    bt->wide_slot = region_wide_slot_bytes(s->Cp, bt->slow_cap);
+    const size_t fit = std::max<size_t>(1, ((size_t)256 << 20) / bt->wide_slot);
+    bt->wide_grid = (int)std::min<size_t>({(size_t)64, bt->l_region_wide.size(), fit});
+  }
   bt->fast_ok = batch_fast_ok(bt);
   Arena& a = bt->dev;
   a.pool_dev = e->device;
@@ -3287,6 +3322,10 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   a.add(&bt->rnsel, std::max(1, nr));
   a.add(&bt->nhost, 1);
   a.add(&bt->slow_scratch, bt->slow_slot * bt->slow_grid);
+  if (!bt->l_region_wide.empty()) {
+    a.add(&bt->d_region_wide, bt->l_region_wide.size());
+    a.add(&bt->wide_scratch, bt->wide_slot * bt->wide_grid);
+  }
   // k_select_top (bits mode): class orders, fallback list. k_class_order sorts a class
   // row in LDS (kRedBytes + 8 * nextpow2(C)): a device with less LDS per workgroup
   // keeps the full-candidate kernels instead of failing the launch.
@@ -3385,6 +3424,8 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   HIPCHK(up(bt->d_all_cls, bt->l_all_cls.data(), 4 * bt->l_all_cls.size()));
   HIPCHK(up(bt->d_cluster, bt->l_cluster.data(), 4 * bt->l_cluster.size()));
   HIPCHK(up(bt->d_region, bt->l_region.data(), 4 * bt->l_region.size()));
+  if (!bt->l_region_wide.empty())
+    HIPCHK(up(bt->d_region_wide, bt->l_region_wide.data(), 4 * bt->l_region_wide.size()));
   HIPCHK(up(bt->d_cs, bt->l_cs.data(), 4 * bt->l_cs.size()));
   HIPCHK(dev::fill(bt->slow, 0, 4 * (size_t)B, e->stream));
   HIPCHK(dev::sync(e->stream));
@@ -3956,6 +3997,17 @@ static int schedule_submit(kp_engine* e, kp_batch* bt) {
       KPROF(st, sel_name(SEL_LAUNCH_REGION_B, smem_region_b(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 13 : -1,
             dev::select(st, SEL_LAUNCH_REGION_B, k, smem_region_b(s, cap), cap, sxa6));
     }
+    // the selections past k_region_b's lists (marked there in a.slow), queued behind it: no
+    // count is read back, a workgroup whose binding carries no mark returns at once
+    if (!bt->l_region_wide.empty()) {
+      KArgs kw = ka;
+      kw.list = bt->d_region;
+      kw.n = nr;
+      const SelectExtra sxw = with_args(kw, st);
+      KPROF(st, "k_region_wide", 0, 17,
+            dev::region_wide(st, kw, sxw, bt->d_region_wide, (int)bt->l_region_wide.size(), bt->wide_scratch,
+                             bt->wide_slot, bt->wide_grid, bt->slow_cap, bt->wide_sort, bt->stats + 17));
+    }
   }
   // k_slow after every kernel that flags bindings (SEL_ALL on stream2, cluster spread on
   // stream3; the region chain, queued above, flags none), beside the region chain. With a
@@ -4186,6 +4238,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
   tm.cluster_kernel_ms = bt->l_cluster.empty() ? 0.f : ems(14, 15);
   tm.n_region = (uint32_t)bt->l_region.size();
   tm.n_region_order = spread_orders ? bt->h_stats[11] : 0u;
+  tm.n_region_wide = bt->l_region_wide.empty() ? 0u : bt->h_stats[17];
 #if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
   {
     std::vector<unsigned long long> hv((size_t)kDbgSlots * kDbgSpread);

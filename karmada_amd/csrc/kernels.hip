@@ -8,6 +8,7 @@
 //                 search, Aggregated cut) over the candidates compacted in LDS.
 // k_select_cluster / k_region_a / k_region_b   spread-constraint selection.
 // k_slow          persistent workgroups: exact serial emulation for flagged bindings.
+// k_region_wide   persistent workgroups: region stage B of selections past k_region_b's LDS lists.
 // k_compact       per-binding results gathered into CSR order.
 #include <hip/hip_runtime.h>
 
@@ -363,6 +364,24 @@ extern "C" __global__ void __launch_bounds__(kSlowBlock) k_slow(const KArgs* __r
 #else
 ;
 #endif
+// Region stage B with the lists in a global slot (kp_kernels.h body_region_wide): persistent
+// workgroups over the batch's wide-listed region bindings, after k_region_b on its stream.
+extern "C" __global__ void __launch_bounds__(kSlowBlock) k_region_wide(const KArgs* __restrict__ pa, const int32_t* wide,
+                                                                       int n_wide, const int32_t* rsel,
+                                                                       const int32_t* rnsel, unsigned char* scratch,
+                                                                       size_t slot_bytes, int cap, int lds_sort,
+                                                                       uint32_t* n_done)
+#if KP_K(8)
+{
+  const KArgs& a = *pa;
+  KP_SMEM;
+  if ((int)blockIdx.x >= n_wide) return;
+  body_region_wide(GpuBlk{(int64_t*)smem}, (int)blockIdx.x, (int)gridDim.x, smem, a, wide, n_wide, rsel, rnsel, scratch,
+                   slot_bytes, cap, lds_sort, n_done);
+}
+#else
+;
+#endif
 extern "C" __global__ void __launch_bounds__(64) k_sets(SnapView s, const SetsArgs* A, const int32_t* ranks, const int64_t* off,
                                                        uint64_t n, int64_t* scratch, int32_t* out)
 #if KP_K(8)
@@ -678,6 +697,19 @@ int select(stream_t st, int which, const KArgs& a, size_t smem, int cap, const S
     default:
       return chk(hipErrorInvalidValue);
   }
+  return chk(hipGetLastError());
+}
+
+int region_wide(stream_t st, const KArgs& a, const SelectExtra& x, const int32_t* wide, int n_wide,
+                unsigned char* scratch, size_t slot_bytes, int grid, int cap, int lds_sort, uint32_t* n_done) {
+  if (n_wide <= 0 || grid <= 0) return 0;
+  if (!x.dargs) return chk(hipErrorInvalidValue);
+  const size_t smem = region_wide_lds_bytes(a.s.Cp, a.s.n_regions, lds_sort);
+  if (smem > 65536 &&
+      chk(hipFuncSetAttribute((const void*)k_region_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)))
+    return -1;
+  hipLaunchKernelGGL(k_region_wide, dim3(grid), dim3(kSlowBlock), smem, (hipStream_t)st, x.dargs, wide, n_wide, x.rsel,
+                     x.rnsel, scratch, slot_bytes, cap, lds_sort, n_done);
   return chk(hipGetLastError());
 }
 

@@ -67,6 +67,13 @@ int est_class(stream_t st, const SnapView& s, const BatchView& bv, const int32_t
 // requires s.n_bits > 0).
 int filter(stream_t st, const SnapView& s, const BatchView& bv, uint64_t* fmask);
 int select(stream_t st, int which, const KArgs& a, size_t smem, int cap, const SelectExtra& x);
+// Region stage B of the wide-listed bindings that k_region_b marked (body_region_wide):
+// `grid` persistent workgroups, each with a slot of slot_bytes in scratch, over the rows
+// wide[0, n_wide) of the region list a.list (x.rsel / x.rnsel by row; x.dargs: a on the
+// device); lds_sort bytes of LDS for the candidate sort (0: in the slot); *n_done counts
+// the bindings it scheduled or errored.
+int region_wide(stream_t st, const KArgs& a, const SelectExtra& x, const int32_t* wide, int n_wide,
+                unsigned char* scratch, size_t slot_bytes, int grid, int cap, int lds_sort, uint32_t* n_done);
 // Estimator-class orders for k_select_top: ord[k][i] = (estimate << 32 | rank) of
 // rows[k] sorted by estimate desc, rank asc; tot[k] its sum; ok[k] whether it can be
 // walked (body_class_order). C <= 16384.

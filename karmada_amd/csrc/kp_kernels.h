@@ -1413,8 +1413,10 @@ KP_FI void body_region_b(const BLK& B, int blk, unsigned char* smem, const KArgs
     if (B.tid() == 0) sink_error(x, KP_STATUS_ERROR, -nsel, 0);
     return;
   }
-  if ((h->flags & BF_DUP_TARGETS) && h->tgt_cnt > kTgtSmallMax) {  // engine limit (selected-list scratch)
-    if (B.tid() == 0) sink_error(x, KP_STATUS_ERROR, KP_ERR_NONE, -1);
+  // A repeated spec.Clusters past the serial scratch of this kernel, or (below) a selection
+  // past its LDS lists: marked for k_region_wide, which runs next on this stream.
+  if ((h->flags & BF_DUP_TARGETS) && h->tgt_cnt > kTgtSmallMax) {
+    if (B.tid() == 0) a.slow[b] = SLOW_REGION_WIDE;
     return;
   }
   KP_STAMP(x, 16);
@@ -1434,7 +1436,9 @@ KP_FI void body_region_b(const BLK& B, int blk, unsigned char* smem, const KArgs
   cd.F = gather(B, x, cd, false);
   region_of_cands(B, a.s, cd);
   KP_STAMP(x, 17);
-  region_b(B, x, cd, rsel + (size_t)blk * R, nsel, hist, heads, rs, items, keys, p, scratch_cap, area_bytes);
+  if (!region_b(B, x, cd, rsel + (size_t)blk * R, nsel, hist, heads, rs, items, keys, p, scratch_cap, area_bytes) &&
+      B.tid() == 0)
+    a.slow[b] = SLOW_REGION_WIDE;
 }
 
 // ---------------------------------------------------------------------------
@@ -1769,6 +1773,156 @@ KP_HD void body_slow(const BLK& B, int blk, int grid, unsigned char* smem, const
     }
     B.sync();
     KP_STAMP(x, 8);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_region_wide: region stage B of the bindings whose selected list outgrew
+// body_region_b's LDS lists (a.slow[b] == SLOW_REGION_WIDE), with every Cp-sized
+// list in a global scratch slot. Persistent: workgroup k handles entries k,
+// k + grid, ... of wide[0, n_wide), each a row of the region list (a.list, rsel,
+// rnsel). selectBestClustersByRegion (select_clusters_by_region.go:41-63): all
+// candidates sorted once by the sortClusters key; a selected region's head is
+// its first entry; the rest are the next restCnt entries of the selected regions
+// that are no heads (candidateClusters, re-sorted there with the same comparator,
+// is this order); then AssignReplicas by the serial emulation over the heads in
+// path order followed by the rest.
+// LDS: [red | spec.Clusters bits | heads 8R | rsel 4R | sort area lds_sort]
+// slot: cand r/v [Cp] | keys [P] | items [Cp] | pos [Cp] | serial scratch
+// ---------------------------------------------------------------------------
+KP_HD inline size_t region_wide_lds_bytes(int Cp, int R, int lds_sort) {
+  const int words = (Cp + 31) >> 5;
+  return kRedBytes + 4 * (size_t)((words + 3) & ~3) + 8 * (size_t)R + 4 * (size_t)((R + 3) & ~3) + 16 + (size_t)lds_sort;
+}
+KP_HD inline size_t region_wide_slot_bytes(int Cp, int cap) {
+  int P = 1;
+  while (P < Cp) P <<= 1;
+  const size_t b = 8 * (size_t)Cp + 8 * (size_t)P + sizeof(Item) * (size_t)Cp + 4 * (size_t)Cp +
+                   serial_scratch_bytes(cap) + 1024;
+  return (b + 255) & ~(size_t)255;
+}
+template <class BLK>
+KP_HD void body_region_wide(const BLK& B, int blk, int grid, unsigned char* smem, const KArgs& a, const int32_t* wide,
+                            int n_wide, const int32_t* rsel, const int32_t* rnsel, unsigned char* scratch,
+                            size_t slot_bytes, int scratch_cap, int lds_sort, uint32_t* n_done) {
+  const int Cp = a.s.Cp, R = a.s.n_regions;
+  const int words = (Cp + 31) >> 5;
+  unsigned char* p = smem + kRedBytes;
+  uint32_t* tgt = (uint32_t*)p;
+  p += 4 * (size_t)((words + 3) & ~3);
+  unsigned long long* heads = (unsigned long long*)p;  // [R] a selected region's first position in the sorted list
+  p += 8 * (size_t)R;
+  int32_t* rs = (int32_t*)p;  // [R] a region's place in the selection path, -1: not selected
+  p += 4 * (size_t)((R + 3) & ~3);
+  unsigned char* sarea = (unsigned char*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
+  unsigned char* mine = scratch + (size_t)blk * slot_bytes;
+  int P = 1;
+  while (P < Cp) P <<= 1;
+  Cands cd;
+  cd.r = (uint32_t*)mine;
+  cd.v = (int32_t*)(cd.r + Cp);
+  cd.g = nullptr;
+  uint64_t* gkeys = (uint64_t*)(cd.v + Cp);
+  uint64_t* keys = (size_t)lds_sort >= 8 * (size_t)P ? (uint64_t*)sarea : gkeys;
+  Item* items = (Item*)(gkeys + P);
+  int32_t* pos = (int32_t*)(items + Cp);
+  unsigned char* ser = (unsigned char*)(pos + Cp);
+  bool fresh = true;  // the slot's rank-indexed scratch is not yet all -1
+  for (int idx = blk; idx < n_wide; idx += grid) {
+    const int row = wide[idx];
+    const int b = a.list[row];
+    // (stage B ran before on this stream; block-uniform) a slot without a marked binding is never touched
+    if (*(volatile int32_t*)&a.slow[b] != SLOW_REGION_WIDE) continue;
+    const int nsel = rnsel[row];
+    const int32_t* sel = rsel + (size_t)row * R;
+    const BindHdr* h = &a.bv.hdr[b];
+    if (fresh) {
+      for (int i = B.tid(); i < Cp; i += B.nth()) pos[i] = -1;
+      fresh = false;
+    }
+    build_bits(B, tgt, words, a.bv.ipool, h->tgt_off, h->tgt_cnt, 2);
+    SelCtx x = make_ctx(a, b, tgt);
+    cd.F = gather(B, x, cd, false);
+    const int F = cd.F;
+    int PF = 1;
+    while (PF < F) PF <<= 1;
+    for (int i = B.tid(); i < PF; i += B.nth()) keys[i] = i < F ? cand_key(x, cd, i, cd.v[i]) : ~0ull;
+    for (int r = B.tid(); r < R; r += B.nth()) {
+      heads[r] = ~0ull;
+      rs[r] = -1;
+    }
+    B.sync();
+    for (int j = B.tid(); j < nsel; j += B.nth()) rs[sel[j]] = j;
+    for (int k = 2; k <= PF; k <<= 1)  // bitonic sort (ascending)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = B.tid(); i < PF; i += B.nth()) {
+          const int l = i ^ j;
+          if (l > i) {
+            const uint64_t ki = keys[i], kl = keys[l];
+            const bool up = (i & k) == 0;
+            if ((ki > kl) == up) {
+              keys[i] = kl;
+              keys[l] = ki;
+            }
+          }
+        }
+        B.sync();
+      }
+    B.sync();
+    auto region_at = [&](int i) {  // the selected region of sorted entry i, or -1
+      const int r = a.s.region_idx[key_rank(keys[i])];
+      return r >= 0 && rs[r] >= 0 ? r : -1;
+    };
+    for (int i = B.tid(); i < F; i += B.nth()) {
+      const int r = region_at(i);
+      if (r >= 0 && heads[r] > (unsigned long long)i) kp_atomic_min_u64(&heads[r], (unsigned long long)i);
+    }
+    B.sync();
+    // the non-head entries of the selected regions, compacted in sorted order; the
+    // first restCnt of them are kept (restCnt is known only after the count: items
+    // holds up to F entries, so every one is written and the list is cut after)
+    int m = 0;
+    for (int t0 = 0; t0 < F; t0 += B.nth()) {
+      const int i = t0 + B.tid();
+      bool e = false;
+      if (i < F) {
+        const int r = region_at(i);
+        e = r >= 0 && heads[r] != (unsigned long long)i;
+      }
+      int32_t tt;
+      const int32_t off = B.excl_scan(e ? 1 : 0, &tt);
+      // (nsel + m + off < F: the heads are nsel entries of the F that are not counted here)
+      if (e && nsel + m + off < Cp) items[nsel + m + off] = item_from_key(x, keys[i]);
+      m += tt;
+    }
+    int nh = 0;  // heads found (a selected region has a feasible cluster: stage A counted it)
+    for (int j = B.tid(); j < nsel; j += B.nth()) {
+      const unsigned long long hp = heads[sel[j]];
+      Item it{};
+      if (hp < (unsigned long long)F) {
+        it = item_from_key(x, keys[hp]);
+        nh++;
+      }
+      items[j] = it;
+    }
+    nh = (int)B.sum64((int64_t)nh);
+    const int64_t total = (int64_t)m + nh;
+    const int64_t needCnt = total < h->cluster_max ? total : h->cluster_max;
+    int64_t restCnt = needCnt - nsel;
+    if (restCnt < 0) restCnt = 0;
+    if (restCnt > m) restCnt = m;
+    const int n = nsel + (int)restCnt;
+    B.sync();
+    if (B.tid() == 0) {
+      SerialScratch sc = serial_scratch_carve(ser, scratch_cap);
+      sc.pos = pos;
+      SerialAssign sa{x, sc, (h->flags & BF_UID_DESC) != 0};
+      SerialOut o = sa.run(items, n);
+      sink_serial(x, sc, o);
+      a.slow[b] = 0;
+      kp_atomic_add(n_done, 1u);
+    }
+    B.sync();
   }
 }
 

@@ -24,6 +24,9 @@ constexpr int kRegionMax = 256;
 // Reasons a binding leaves the fast paths for the exact serial path (stats[reason]).
 enum : int { SLOW_NONE = 0, SLOW_OVERFLOW_DUP = 1, SLOW_SCALE_DOWN = 2, SLOW_WRAP = 3, SLOW_TIE = 4, SLOW_WEIGHT = 5,
              SLOW_CLUSTER = 6,
+             // a.slow[b] of a region-spread binding whose selection outgrew stage B's LDS lists:
+             // k_region_wide's mark (not a k_slow reason: k_slow never covers region bindings)
+             SLOW_REGION_WIDE = 7,
              SLOW_TOP_FULL = 100 };  // k_select_top only: the binding needs the full candidate set (not a k_slow reason)
 
 KP_HD inline uint64_t cand_key(const SelCtx& x, const Cands& cd, int i, int32_t est) {
@@ -1397,8 +1400,11 @@ KP_FI void region_a(const BLK& B, const SelCtx& x, const Cands& cd, RegionLds L,
 // (select_clusters_by_region.go:41-63). sel: selected region ids in path order.
 // ----------------------------------------------------------------------------
 // n_sel: as sel_cluster_fast's (the selection only, no assignment).
+// Returns false, with nothing written, when the selected list (needCnt clusters)
+// does not fit the kSmallMax items: the binding then takes the wide path
+// (body_region_wide), whose lists live in a global slot.
 template <class BLK, bool kKeyed = false>
-KP_FI void region_b(const BLK& B, const SelCtx& x, const Cands& cd, const int32_t* sel, int nsel, uint32_t* hist,
+KP_FI bool region_b(const BLK& B, const SelCtx& x, const Cands& cd, const int32_t* sel, int nsel, uint32_t* hist,
                     unsigned long long* heads, int32_t* rsel, Item* items, uint64_t* keys, void* scratch, int cap,
                     size_t area_bytes, int* n_sel = nullptr) {
   if (n_sel) *n_sel = -1;
@@ -1493,10 +1499,7 @@ KP_FI void region_b(const BLK& B, const SelCtx& x, const Cands& cd, const int32_
   const int64_t total = *ctr;
   int64_t needCnt = total < h.cluster_max ? total : h.cluster_max;
   int64_t restCnt = needCnt - nsel;
-  if (restCnt > kSmallMax - nsel) {  // engine limit: selected list capacity
-    if (B.tid() == 0) sink_error(x, KP_STATUS_ERROR, KP_ERR_NONE, -1);
-    return;
-  }
+  if (restCnt > kSmallMax - nsel) return false;  // (block-uniform) past the LDS lists: the wide path
   for (int j = B.tid(); j < nsel; j += B.nth()) items[j] = item_from_key(x, heads[sel[j]]);
   int n = nsel;
   B.sync();
@@ -1544,10 +1547,11 @@ KP_FI void region_b(const BLK& B, const SelCtx& x, const Cands& cd, const int32_
   KP_STAMP(x, 19);
   if (n_sel) {
     *n_sel = n;
-    return;
+    return true;
   }
   assign_small(B, x, items, n, scratch, cap, area_bytes);
   KP_STAMP(x, 20);
+  return true;
 }
 
 }  // namespace kp

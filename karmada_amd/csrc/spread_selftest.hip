@@ -140,7 +140,7 @@ KP_HD void run_case(const BLK& B, unsigned char* ws, const Case& c) {
         if (B.tid() == 0) sink_error(x, KP_STATUS_ERROR, -nsel, 0);
         break;
       }
-      region_b<BLK, true>(B, x, cd, c.sel, nsel, hist, heads, rs, items, keys, nullptr, 0, 0, &n);
+      if (!region_b<BLK, true>(B, x, cd, c.sel, nsel, hist, heads, rs, items, keys, nullptr, 0, 0, &n)) n = -3;
       break;
     }
     case OP_CLUSTER:
