@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define KP_ABI_VERSION 14
+#define KP_ABI_VERSION 15
 
 /* ------------------------------------------------------------------------- */
 /* Object model                                                              */
@@ -347,6 +347,32 @@ typedef struct kp_results {
   uint64_t n_targets;
 } kp_results;
 
+/* The packed form of kp_results (kp_schedule_batch_packed): 4 bytes per target where
+ * kp_results has 8, for a caller that walks the result once. n_bindings, status,
+ * err_code, err_arg, offsets and n_targets hold exactly what kp_results holds for the
+ * same call, and entry i of `targets` is entry i of cluster_idx / replicas:
+ *   bits [15:0]  the caller's cluster index (a batch never has more than 65 536 clusters);
+ *   bits [31:16] the replicas, or 0xFFFF when they lie outside 0..65534 (negative values
+ *                and 65535 itself included): the entry is then "escaped".
+ * The escaped entries' replicas stand in wide_replicas in entry order: the k-th 0xFFFF
+ * entry of `targets` takes wide_replicas[k]. The escaped entries of binding b are
+ * wide_replicas[wide_offsets[b] .. wide_offsets[b+1]), so one binding decodes from
+ * offsets[b] and wide_offsets[b] alone; wide_offsets (n_bindings + 1) may be NULL when
+ * n_wide == 0. kp_results_unpack is the decoder's definition. Engine-owned, valid until
+ * the next call on the engine, as kp_results. */
+typedef struct kp_results_packed {
+  uint64_t n_bindings;
+  const int32_t* status;
+  const int32_t* err_code;
+  const int64_t* err_arg;
+  const uint64_t* offsets; /* n_bindings + 1 */
+  const uint32_t* targets; /* n_targets packed words */
+  uint64_t n_targets;
+  const int32_t* wide_replicas; /* n_wide escaped replicas, entry order */
+  uint64_t n_wide;
+  const uint64_t* wide_offsets; /* n_bindings + 1, or NULL when n_wide == 0 */
+} kp_results_packed;
+
 /* Results of kp_schedule_affinities, engine-owned like kp_results. `results` holds
  * each binding's final Schedule outcome: the first successful term's targets, or,
  * when every term failed, the FIRST term's error class/code/arg with no targets
@@ -491,6 +517,23 @@ int kp_schedule_batch(kp_engine* e, kp_batch* b, kp_results* out);
  * kp_engine_set_profile (KP_EINVAL). */
 int kp_schedule_batch_submit(kp_engine* e, kp_batch* b);
 int kp_schedule_batch_collect(kp_engine* e, kp_batch* b, kp_results* out);
+
+/* kp_schedule_batch with the results in the packed form (kp_results_packed): the same
+ * kernels, then the result gathered as one packed word per target plus the escaped
+ * replicas, so half the bytes cross the bus unless most entries are escaped.
+ * _submit_packed / _collect_packed are the two halves with the contract of
+ * kp_schedule_batch_submit / _collect: one submitted call per batch in either format
+ * (KP_ESTATE on a second submit, or on a collect with nothing submitted; KP_EINVAL with
+ * kp_engine_set_profile). A submitted call is collected by its own format's function:
+ * the other one returns KP_ESTATE and leaves the call collectable. A batch may be
+ * scheduled in either format from call to call. KP_ENOTSUP for a snapshot of more than
+ * 65 536 clusters. */
+int kp_schedule_batch_packed(kp_engine* e, kp_batch* b, kp_results_packed* out);
+int kp_schedule_batch_submit_packed(kp_engine* e, kp_batch* b);
+int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* b, kp_results_packed* out);
+/* Expands packed results into caller-provided arrays of in->n_targets entries each, the
+ * cluster_idx / replicas of kp_results. Plain host code: no engine, no device. */
+int kp_results_unpack(const kp_results_packed* in, uint32_t* cluster_idx, int32_t* replicas);
 
 /* Scheduler.scheduleResourceBindingWithClusterAffinities (scheduler.go:618-684),
  * batched: bindings with n_cluster_affinities > 0 start at getAffinityIndex of their

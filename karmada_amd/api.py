@@ -173,6 +173,16 @@ class kp_results(C.Structure):
                 ("cluster_idx", C.POINTER(u32)), ("replicas", C.POINTER(i32)), ("n_targets", u64)]
 
 
+class kp_results_packed(C.Structure):
+    """kp_results in 4 bytes per target: targets[i] = cluster index | replicas << 16, the
+    replicas 0xFFFF when outside 0..65534 and then the next entry of wide_replicas
+    (kp_api.h; kp_results_unpack decodes)."""
+    _fields_ = [("n_bindings", u64), ("status", C.POINTER(i32)), ("err_code", C.POINTER(i32)),
+                ("err_arg", C.POINTER(i64)), ("offsets", C.POINTER(u64)),
+                ("targets", C.POINTER(u32)), ("n_targets", u64),
+                ("wide_replicas", C.POINTER(i32)), ("n_wide", u64), ("wide_offsets", C.POINTER(u64))]
+
+
 class kp_binding_key(C.Structure):
     _fields_ = [("uid", kp_str), ("generation", i64)]
 

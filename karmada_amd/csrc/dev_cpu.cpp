@@ -336,6 +336,18 @@ int compact(stream_t, const uint64_t* start, const uint32_t* count, const uint64
     body_compact(CpuBlk{red}, b, start, count, offsets, in_idx, in_rep, out_idx, out_rep, n, perm, h_idx, h_rep, h_cap);
   return 0;
 }
+int pack(stream_t, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx, const int32_t* in_rep,
+         uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm) {
+  int64_t red[8];
+  for (int b = 0; b < n; b++) body_pack(CpuBlk{red}, b, start, offsets, in_idx, in_rep, out, wide_count, n, perm);
+  return 0;
+}
+int pack_wide(stream_t, const uint64_t* start, const uint64_t* offsets, const uint64_t* wide_offsets,
+              const int32_t* in_rep, int32_t* out, int n) {
+  int64_t red[8];
+  for (int b = 0; b < n; b++) body_pack_wide(CpuBlk{red}, b, start, offsets, wide_offsets, in_rep, out, n);
+  return 0;
+}
 int host_device_ptr(void* host, void** dev) {
   *dev = host;
   return 0;

@@ -373,6 +373,7 @@ struct kp_snapshot {
 // The state schedule_submit leaves for schedule_finish (one submitted call per batch).
 struct SchedPend {
   bool live = false, empty = false, zc = false, bits = false, top = false, spread_orders = false;
+  bool packed = false;  // the call returns kp_results_packed (kp_schedule_batch_submit_packed)
   int fast = 0;
   double t0 = 0, th0 = 0, th1 = 0;
   uint64_t spec = 0, seq = 0;
@@ -481,6 +482,14 @@ struct kp_batch {
   uint64_t last_tot = 0;  // the previous call's CSR size (the speculative copy)
   SchedPend pend;         // a submitted call (schedule_submit) awaiting schedule_finish
   size_t h_cidx_bytes = 0, h_crep_bytes = 0;  // their pooled block sizes
+  // The packed result form (kp_results_packed), allocated on the batch's first packed call
+  // (ensure_packed): per-binding escape counts [B] and their scan [B + 1] on the device,
+  // the scan's page-locked host copy. The packed words take cidx_d / h_cidx and the
+  // escaped replicas crep_d / h_crep, which a packed call does not otherwise use.
+  uint32_t* wcount_d = nullptr;
+  uint64_t* woff_d = nullptr;
+  uint64_t* h_woff = nullptr;
+  size_t h_woff_bytes = 0;
   // The batch's device arena and page-locked buffers go back to the process-wide
   // pools on destruction, where another batch (of any engine) may take them at
   // once. An entry point that fails part-way leaves kernels queued that still
@@ -512,7 +521,9 @@ struct kp_batch {
     buf_pool().put(-1, h_cidx, h_cidx_bytes);
     buf_pool().put(-1, h_crep, h_crep_bytes);
     buf_pool().put(-1, h_kargs, h_kargs_bytes);
+    buf_pool().put(-1, h_woff, h_woff_bytes);
     if (est) dev::release(est);
+    if (wcount_d) dev::release(wcount_d);  // (one allocation: woff_d lies behind the counts)
   }
   std::vector<RegionOut> h_rout;
 };
@@ -3480,6 +3491,30 @@ static int ensure_rows(kp_engine* e, kp_batch* bt) {
   return 0;
 }
 
+// The packed result form's buffers, allocated on the batch's first packed call (a batch
+// only ever scheduled through kp_schedule_batch never needs them).
+static int ensure_packed(kp_engine* e, kp_batch* bt) {
+  const size_t B = (size_t)std::max(1, bt->B);
+  if (!bt->wcount_d) {
+    const size_t cnt = (4 * B + 255) & ~(size_t)255;  // the counts, then the 8-byte-aligned scan
+    void* p = nullptr;
+    if (dev::alloc(&p, cnt + 8 * (B + 1))) {
+      e->err = std::string("packed results: ") + dev::last_error();
+      return -1;
+    }
+    bt->wcount_d = (uint32_t*)p;
+    bt->woff_d = (uint64_t*)((char*)p + cnt);
+  }
+  if (!bt->h_woff) {
+    bt->h_woff = (uint64_t*)pinned_get(8 * (B + 1), &bt->h_woff_bytes);
+    if (!bt->h_woff) {
+      e->err = "packed results: page-locked wide_offsets";
+      return -1;
+    }
+  }
+  return 0;
+}
+
 // Per-kernel profiling (kp_engine_set_profile): prof_begin records the start event of
 // launch i on its stream, prof_end its end event and what it covered.
 static int prof_begin(kp_engine* e, dev::stream_t st) {
@@ -3581,12 +3616,20 @@ static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s) {
 // schedule_finish waits for that event, copies the CSR back and fills the results.
 // kp_schedule_batch runs both; kp_schedule_batch_submit / _collect let a caller keep the
 // next batch's kernels queued on the engine's stream while it collects the previous one.
-static int schedule_submit(kp_engine* e, kp_batch* bt) {
+// packed: the results are gathered in the packed form (k_pack, the escape counts' scan,
+// k_pack_wide) instead of the CSR (k_compact), for schedule_finish to return as
+// kp_results_packed.
+static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
   if (!e || !bt) return KP_EINVAL;
   if (int rc = refuse_out_of_tree(e, bt->snap)) return rc;
   (void)dev::set_device(e->device);
   kp_snapshot* s = bt->snap;
   const int B = bt->B;
+  if (packed && s->C > 65536) {  // (kp_batch_create's LDS bound refuses such snapshots long before)
+    e->err = "kp_schedule_batch_packed: a packed cluster index holds 16 bits (more than 65536 clusters)";
+    return KP_ENOTSUP;
+  }
+  if (packed && ensure_packed(e, bt)) return KP_EDEVICE;
   double t0 = now_ms();
   kp_stage_times tm{};
   dev::stream_t st = e->stream;
@@ -3596,6 +3639,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt) {
     pd = SchedPend{};
     pd.ev = ev;
   }
+  pd.packed = packed;
   pd.t0 = t0;
   pd.seq = ++e->submit_seq;
   if (B == 0) {
@@ -4077,16 +4121,27 @@ static int schedule_submit(kp_engine* e, kp_batch* bt) {
   // GPU while each one reads its total back). A total past the capacity takes the copy.
   uint32_t* zc_idx = nullptr;
   int32_t* zc_rep = nullptr;
-  if (e->zc && bt->h_cidx && bt->h_crep && bt->h_res_cap > 0) {
+  if (packed) {
+    // the packed form: one word per target into cidx_d, the escape counts scanned into
+    // wide_offsets (the CSR scan's chunk totals are consumed by now: one stream), the
+    // escaped replicas into crep_d; the zero-copy and speculative-copy paths stay wide-only
+    KPROF(st, "k_pack", B, -1,
+          dev::pack(st, bt->start, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->wcount_d, B, s->view.perm));
+    KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->wcount_d, B, bt->woff_d, bt->off_part));
+    KPROF(st, "k_pack_wide", B, -1,
+          dev::pack_wide(st, bt->start, bt->offsets_d, bt->woff_d, bt->out_rep, bt->crep_d, B));
+    HIPCHK(dev::d2h(bt->h_woff, bt->woff_d, 8 * (size_t)(B + 1), st));
+  } else if (e->zc && bt->h_cidx && bt->h_crep && bt->h_res_cap > 0) {
     void *di = nullptr, *dr = nullptr;
     if (dev::host_device_ptr(bt->h_cidx, &di) == 0 && dev::host_device_ptr(bt->h_crep, &dr) == 0) {
       zc_idx = (uint32_t*)di;
       zc_rep = (int32_t*)dr;
     }
   }
-  KPROF(st, "k_compact", B, -1,
-        dev::compact(st, bt->start, bt->count, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->crep_d, B,
-                     s->view.perm, zc_idx, zc_rep, zc_idx ? bt->h_res_cap : 0));
+  if (!packed)
+    KPROF(st, "k_compact", B, -1,
+          dev::compact(st, bt->start, bt->count, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->crep_d, B,
+                       s->view.perm, zc_idx, zc_rep, zc_idx ? bt->h_res_cap : 0));
   bt->h_status.resize(B);
   bt->h_err.resize(B);
   bt->h_arg.resize(B);
@@ -4107,7 +4162,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt) {
   // this call's total (the rest, if this total is larger, after it): one host round trip
   // per call instead of two, so the stream has the copy queued behind the kernels.
   uint64_t spec = 0;
-  if (!zc_idx && bt->h_cidx && bt->h_crep && e->spec_copy) {
+  if (!packed && !zc_idx && bt->h_cidx && bt->h_crep && e->spec_copy) {
     spec = std::min<uint64_t>(bt->last_tot, bt->h_res_cap);
     if (spec) {
       HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * spec, st));
@@ -4125,11 +4180,19 @@ static int schedule_submit(kp_engine* e, kp_batch* bt) {
   return KP_OK;
 }
 
-static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
-  if (!e || !bt || !out) return KP_EINVAL;
+// Exactly one of out / pout is given: the format the caller collects in, which must be
+// the one the call was submitted in.
+static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout = nullptr) {
+  if (!e || !bt || (!out && !pout)) return KP_EINVAL;
   SchedPend& pd = bt->pend;
   if (!pd.live) {
     e->err = "kp_schedule_batch_collect: the batch has no submitted call";
+    return KP_ESTATE;
+  }
+  const bool packed = pout != nullptr;
+  if (pd.packed != packed) {  // (the call stays submitted, for the right function to collect)
+    e->err = pd.packed ? "kp_schedule_batch_collect: the submitted call is packed (kp_schedule_batch_collect_packed)"
+                       : "kp_schedule_batch_collect_packed: the submitted call is not packed (kp_schedule_batch_collect)";
     return KP_ESTATE;
   }
   pd.live = false;
@@ -4137,9 +4200,14 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
   kp_snapshot* s = bt->snap;
   const int B = bt->B;
   if (pd.empty) {
-    memset(out, 0, sizeof(*out));
     bt->h_offsets.assign(1, 0);
-    out->offsets = bt->h_offsets.data();
+    if (packed) {
+      memset(pout, 0, sizeof(*pout));
+      pout->offsets = bt->h_offsets.data();
+    } else {
+      memset(out, 0, sizeof(*out));
+      out->offsets = bt->h_offsets.data();
+    }
     return KP_OK;
   }
   dev::stream_t st = e->stream;
@@ -4177,7 +4245,14 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
     }
     bt->h_res_cap = std::min(bt->h_cidx_bytes, bt->h_crep_bytes) / 4;
   }
-  if (copy && tot > have) {
+  // (a packed call: tot packed words in cidx_d and the n_wide <= tot escaped replicas in
+  // crep_d, 4 * (tot + n_wide) bytes instead of 8 * tot; submitted with zc and spec off)
+  uint64_t n_wide = packed ? bt->h_woff[B] : 0;
+  if (packed) {
+    if (tot) HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * tot, st));
+    if (n_wide) HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * n_wide, st));
+    if (tot) HIPCHK(dev::sync(st));
+  } else if (copy && tot > have) {
     HIPCHK(dev::d2h(bt->h_cidx + have, bt->cidx_d + have, 4 * (tot - have), st));
     HIPCHK(dev::d2h(bt->h_crep + have, bt->crep_d + have, 4 * (tot - have), st));
     HIPCHK(dev::sync(st));
@@ -4196,10 +4271,18 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
       }
   }
   if (std::any_of(sets_ovf.begin(), sets_ovf.end(), [](uint32_t v) { return v != 0; })) {
-    uint64_t w = 0;
+    uint64_t w = 0, ww = 0;  // (packed: h_cidx holds the words, h_crep the escaped replicas)
     for (int b = 0; b < B; b++) {
       const uint64_t lo = bt->h_offsets[b], hi = bt->h_offsets[b + 1];
       bt->h_offsets[b] = w;
+      if (packed) {
+        const uint64_t wlo = bt->h_woff[b], whi = bt->h_woff[b + 1];
+        bt->h_woff[b] = ww;
+        if (bt->h_status[b] != KP_STATUS_OK) continue;
+        for (uint64_t k = lo; k < hi; k++, w++) bt->h_cidx[w] = bt->h_cidx[k];
+        for (uint64_t k = wlo; k < whi; k++, ww++) bt->h_crep[ww] = bt->h_crep[k];
+        continue;
+      }
       if (bt->h_status[b] != KP_STATUS_OK) continue;
       for (uint64_t k = lo; k < hi; k++, w++) {
         bt->h_cidx[w] = bt->h_cidx[k];
@@ -4207,6 +4290,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
       }
     }
     bt->h_offsets[B] = w;
+    if (packed) bt->h_woff[B] = n_wide = ww;
   }
   const uint64_t tot_out = bt->h_offsets[B];
   double t1 = now_ms();
@@ -4265,6 +4349,19 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out) {
   tm.copy_ms = t1 - tc0;
   tm.total_ms = t1 - t0;
   e->times = tm;
+  if (packed) {
+    pout->n_bindings = (uint64_t)B;
+    pout->status = bt->h_status.data();
+    pout->err_code = bt->h_err.data();
+    pout->err_arg = bt->h_arg.data();
+    pout->offsets = bt->h_offsets.data();
+    pout->targets = bt->h_cidx;
+    pout->n_targets = tot_out;
+    pout->wide_replicas = bt->h_crep;
+    pout->n_wide = n_wide;
+    pout->wide_offsets = bt->h_woff;
+    return KP_OK;
+  }
   out->n_bindings = (uint64_t)B;
   out->status = bt->h_status.data();
   out->err_code = bt->h_err.data();
@@ -4294,6 +4391,45 @@ int kp_schedule_batch_submit(kp_engine* e, kp_batch* bt) {
 }
 int kp_schedule_batch_collect(kp_engine* e, kp_batch* bt, kp_results* out) {
   return batch_fence(e, bt, schedule_finish(e, bt, out));
+}
+
+// The packed result form (kp_results_packed): the same calls with packed = true.
+static int schedule_batch_packed_impl(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
+  if (!out) return KP_EINVAL;
+  if (int rc = schedule_submit(e, bt, true)) return rc;
+  return schedule_finish(e, bt, nullptr, out);
+}
+int kp_schedule_batch_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
+  return batch_fence(e, bt, schedule_batch_packed_impl(e, bt, out));
+}
+int kp_schedule_batch_submit_packed(kp_engine* e, kp_batch* bt) {
+  if (e && e->prof) {
+    e->err = "kp_schedule_batch_submit_packed: per-kernel profiling covers kp_schedule_batch only";
+    return KP_EINVAL;
+  }
+  if (e && bt && bt->pend.live) {
+    e->err = "kp_schedule_batch_submit_packed: the batch's previous call is not collected";
+    return KP_ESTATE;
+  }
+  return batch_fence(e, bt, schedule_submit(e, bt, true));
+}
+int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
+  return batch_fence(e, bt, schedule_finish(e, bt, nullptr, out));
+}
+int kp_results_unpack(const kp_results_packed* in, uint32_t* cluster_idx, int32_t* replicas) {
+  if (!in || (in->n_targets && (!in->targets || !cluster_idx || !replicas))) return KP_EINVAL;
+  uint64_t k = 0;  // the escape cursor: the next entry of wide_replicas
+  for (uint64_t i = 0; i < in->n_targets; i++) {
+    const uint32_t w = in->targets[i];
+    cluster_idx[i] = w & 0xFFFFu;
+    if ((w >> 16) != 0xFFFFu) {
+      replicas[i] = (int32_t)(w >> 16);
+    } else {
+      if (k >= in->n_wide || !in->wide_replicas) return KP_EINVAL;  // more escapes than wide entries
+      replicas[i] = in->wide_replicas[k++];
+    }
+  }
+  return k == in->n_wide ? KP_OK : KP_EINVAL;
 }
 
 // Runs the pair kernel and returns the rank-ordered device row pointers.

@@ -10,6 +10,7 @@
 // k_slow          persistent workgroups: exact serial emulation for flagged bindings.
 // k_region_wide   persistent workgroups: region stage B of selections past k_region_b's LDS lists.
 // k_compact       per-binding results gathered into CSR order.
+// k_pack / k_pack_wide   the same into the packed form (one word per target + escaped replicas).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -494,6 +495,30 @@ extern "C" __global__ void __launch_bounds__(64) k_compact(const uint64_t* start
 #else
 ;
 #endif
+// The packed result form: k_pack in k_compact's place, then k_offsets_a / _b over the
+// escape counts, then k_pack_wide; one wave64 per binding (the ballots are the wave's).
+extern "C" __global__ void __launch_bounds__(64) k_pack(const uint64_t* start, const uint64_t* offsets,
+                                                        const uint32_t* in_idx, const int32_t* in_rep, uint32_t* out,
+                                                        uint32_t* wide_count, int n, const uint32_t* perm)
+#if KP_K(8)
+{
+  __shared__ int64_t red[8];
+  body_pack(GpuBlk{red}, (int)blockIdx.x, start, offsets, in_idx, in_rep, out, wide_count, n, perm);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64) k_pack_wide(const uint64_t* start, const uint64_t* offsets,
+                                                             const uint64_t* wide_offsets, const int32_t* in_rep,
+                                                             int32_t* out, int n)
+#if KP_K(8)
+{
+  __shared__ int64_t red[8];
+  body_pack_wide(GpuBlk{red}, (int)blockIdx.x, start, offsets, wide_offsets, in_rep, out, n);
+}
+#else
+;
+#endif
 
 // ---------------------------------------------------------------------------
 // Device interface (HIP)
@@ -868,6 +893,19 @@ int compact(stream_t st, const uint64_t* start, const uint32_t* count, const uin
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_compact, dim3(n), dim3(64), 0, (hipStream_t)st, start, count, offsets, in_idx, in_rep, out_idx,
                      out_rep, n, perm, h_idx, h_rep, h_cap);
+  return chk(hipGetLastError());
+}
+int pack(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx, const int32_t* in_rep,
+         uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_pack, dim3(n), dim3(64), 0, (hipStream_t)st, start, offsets, in_idx, in_rep, out, wide_count, n,
+                     perm);
+  return chk(hipGetLastError());
+}
+int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint64_t* wide_offsets,
+              const int32_t* in_rep, int32_t* out, int n) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_pack_wide, dim3(n), dim3(64), 0, (hipStream_t)st, start, offsets, wide_offsets, in_rep, out, n);
   return chk(hipGetLastError());
 }
 int host_device_ptr(void* host, void** dev) { return chk(hipHostGetDevicePointer(dev, host, 0)); }

@@ -160,16 +160,21 @@ struct GpuBlk {
       u = opd(u, a[48 + w]);
     }
   }
-  // This thread's slot base for `mine` entries in a list filled by every wave
-  // independently: the wave reserves its total with one LDS atomic on *ctr
-  // (zeroed beforehand, behind a barrier). No barrier; slot order across
-  // waves is not deterministic, within a wave it follows the lanes.
+  // This thread's slot base for `mine` entries in a list every thread fills: the
+  // slots follow the thread order (the waves' totals are exchanged through the
+  // scratch area, one barrier), so the list, and with it the order in which a
+  // binding's results are emitted, is the same from run to run. *ctr (zeroed
+  // beforehand, behind a barrier) receives the list's length. Block-uniform call.
   KP_INLINE int32_t wave_reserve(int32_t mine, uint32_t* ctr) const {
     const int32_t incl = wave_incl_scan(mine);
-    const int32_t tot = kp_readlane(incl, 63);
+    int64_t* a = area();
+    if (lane() == 63) {
+      a[wid()] = incl;
+      if (incl > 0) atomicAdd(ctr, (uint32_t)incl);
+    }
+    sync();
     int32_t base = 0;
-    if (lane() == 63 && tot > 0) base = (int32_t)atomicAdd(ctr, (uint32_t)tot);
-    base = kp_readlane(base, 63);
+    for (int w = 0; w < wid(); w++) base += (int32_t)a[w];
     return base + incl - mine;
   }
   KP_INLINE int64_t sum64(int64_t v) const { return reduce(v, [](int64_t a, int64_t b) { return a + b; }, (int64_t)0); }

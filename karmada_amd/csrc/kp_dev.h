@@ -132,6 +132,15 @@ int offsets(stream_t st, const int32_t* status, const uint32_t* count, int n, ui
 int compact(stream_t st, const uint64_t* start, const uint32_t* count, const uint64_t* offsets, const uint32_t* in_idx,
             const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm,
             uint32_t* h_idx = nullptr, int32_t* h_rep = nullptr, uint64_t h_cap = 0);
+// The packed result form (kp_results_packed), in compact's place: out[offsets[b] + i] = the
+// packed word of binding b's entry i (perm[rank] | replicas << 16, 0xFFFF for escaped
+// replicas) and wide_count[b] = its escaped entries (body_pack); then, with wide_offsets
+// scanned from those counts (offsets above), the escaped replicas in entry order at
+// out[wide_offsets[b] ..] (body_pack_wide).
+int pack(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx, const int32_t* in_rep,
+         uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm);
+int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint64_t* wide_offsets,
+              const int32_t* in_rep, int32_t* out, int n);
 // The device address of page-locked host memory from host_alloc (the same on the host build).
 int host_device_ptr(void* host, void** dev);
 

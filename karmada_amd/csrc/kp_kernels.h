@@ -1991,4 +1991,57 @@ KP_FI void body_compact(const BLK& B, int blk, const uint64_t* start, const uint
   }
 }
 
+// The packed result form (kp_results_packed): one word per target, the caller's cluster
+// index in bits [15:0] and the replicas in bits [31:16], 0xFFFF there for replicas outside
+// 0..65534 (an escaped entry, whose replicas go to the wide list). A packed call runs
+// body_pack instead of body_compact, then body_offsets over the per-binding escape counts,
+// then body_pack_wide. One wave (B.nth() == B.wwidth() threads) per binding.
+KP_HD inline bool pack_escaped(int32_t rep) { return (uint32_t)rep >= 0xFFFFu; }  // negative, or >= 65535
+
+// Gathers binding blk's results as packed words at offsets[blk] + i and counts its
+// escaped entries into wide_count[blk] (0 for a binding without targets).
+template <class BLK>
+KP_FI void body_pack(const BLK& B, int blk, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx,
+                     const int32_t* in_rep, uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm) {
+  if (blk >= n) return;
+  const uint64_t s = start[blk], o = offsets[blk];
+  const uint32_t c = (uint32_t)(offsets[blk + 1] - o);  // 0 unless the status is OK (body_offsets)
+  uint32_t nesc = 0;
+  for (uint32_t base = 0; base < c; base += (uint32_t)B.nth()) {  // (wave-uniform trip count: the ballot)
+    const uint32_t i = base + (uint32_t)B.tid();
+    bool esc = false;
+    if (i < c) {
+      const uint32_t ci = perm[in_idx[s + i]];
+      const int32_t cr = in_rep[s + i];
+      esc = pack_escaped(cr);
+      out[o + i] = (ci & 0xFFFFu) | ((esc ? 0xFFFFu : (uint32_t)cr) << 16);
+    }
+    nesc += (uint32_t)popc64(B.wballot(esc));
+  }
+  if (B.tid() == 0) wide_count[blk] = nesc;
+}
+
+// Writes binding blk's escaped replicas at wide_offsets[blk] + rank, rank = the entry's
+// position among the binding's escaped entries in entry order: a ballot and the count of
+// escaped lanes below within each 64-entry iteration, the running count carried across
+// iterations. No atomics: the output is the same from run to run.
+template <class BLK>
+KP_FI void body_pack_wide(const BLK& B, int blk, const uint64_t* start, const uint64_t* offsets,
+                          const uint64_t* wide_offsets, const int32_t* in_rep, int32_t* out, int n) {
+  if (blk >= n) return;
+  const uint64_t wo = wide_offsets[blk];
+  if (wide_offsets[blk + 1] == wo) return;  // no escaped entry
+  const uint64_t s = start[blk];
+  const uint32_t c = (uint32_t)(offsets[blk + 1] - offsets[blk]);
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < c; base += (uint32_t)B.nth()) {
+    const uint32_t i = base + (uint32_t)B.tid();
+    const int32_t cr = i < c ? in_rep[s + i] : 0;
+    const bool esc = i < c && pack_escaped(cr);
+    const uint64_t m = B.wballot(esc);
+    if (esc) out[wo + run + (uint32_t)popc64(m & B.wlt())] = cr;
+    run += (uint32_t)popc64(m);
+  }
+}
+
 }  // namespace kp

@@ -25,7 +25,7 @@ from karmada_amd import api
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libkp.so")
-KP_ABI_VERSION = 14
+KP_ABI_VERSION = 15
 
 _LIBS = {}
 
@@ -35,7 +35,9 @@ EXPORTS = (
     "kp_snapshot_destroy", "kp_snapshot_export", "kp_snapshot_import", "kp_snapshot_update", "kp_batch_create",
     "kp_batch_destroy", "kp_batch_create_keyed", "kp_batch_digest", "kp_pack_cache_create", "kp_pack_cache_destroy",
     "kp_pack_cache_get_stats",
-    "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect", "kp_schedule_affinities", "kp_filter_batch", "kp_filter_reasons", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
+    "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
+    "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
+    "kp_schedule_affinities", "kp_filter_batch", "kp_filter_reasons", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
     "kp_multi_create", "kp_multi_destroy", "kp_multi_last_error", "kp_multi_devices", "kp_multi_engine",
@@ -79,6 +81,10 @@ def load_library(path: str = LIB_PATH):
     L.kp_schedule_batch.argtypes = [vp, vp, C.POINTER(api.kp_results)]
     L.kp_schedule_batch_submit.argtypes = [vp, vp]
     L.kp_schedule_batch_collect.argtypes = [vp, vp, C.POINTER(api.kp_results)]
+    L.kp_schedule_batch_packed.argtypes = [vp, vp, C.POINTER(api.kp_results_packed)]
+    L.kp_schedule_batch_submit_packed.argtypes = [vp, vp]
+    L.kp_schedule_batch_collect_packed.argtypes = [vp, vp, C.POINTER(api.kp_results_packed)]
+    L.kp_results_unpack.argtypes = [C.POINTER(api.kp_results_packed), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.kp_schedule_affinities.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64,
                                          C.POINTER(api.kp_affinity_results)]
     L.kp_filter_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
@@ -393,8 +399,42 @@ class Batch:
         eng._check(eng.L.kp_schedule_batch_collect(eng.h, self.h, C.byref(r)), "kp_schedule_batch_collect")
         return r
 
-    def schedule(self) -> List[dict]:
-        """Results as api.results_to_python dicts (cluster indices in snapshot input order)."""
+    def schedule_packed_raw(self) -> api.kp_results_packed:
+        """kp_schedule_batch_packed: the results in 4 bytes per target (api.kp_results_packed)."""
+        r = api.kp_results_packed()
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_packed(eng.h, self.h, C.byref(r)), "kp_schedule_batch_packed")
+        return r
+
+    def submit_packed(self):
+        """kp_schedule_batch_submit_packed: submit() for a call collected by collect_packed()."""
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_submit_packed(eng.h, self.h), "kp_schedule_batch_submit_packed")
+
+    def collect_packed(self) -> api.kp_results_packed:
+        """kp_schedule_batch_collect_packed: the results of the call submit_packed() queued."""
+        r = api.kp_results_packed()
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_collect_packed(eng.h, self.h, C.byref(r)),
+                   "kp_schedule_batch_collect_packed")
+        return r
+
+    def unpack(self, r: api.kp_results_packed):
+        """kp_results_unpack: (cluster_idx, replicas) ctypes arrays of r.n_targets entries."""
+        ci = (C.c_uint32 * max(1, r.n_targets))()
+        rep = (C.c_int32 * max(1, r.n_targets))()
+        eng = self.snap.engine
+        if eng.L.kp_results_unpack(C.byref(r), ci, rep) != KP_OK:
+            raise EngineError("kp_results_unpack: the packed results are inconsistent")
+        return ci, rep
+
+    def schedule(self, packed: bool = False) -> List[dict]:
+        """Results as api.results_to_python dicts (cluster indices in snapshot input order).
+        packed: through kp_schedule_batch_packed and kp_results_unpack (the same dicts)."""
+        if packed:
+            p = self.schedule_packed_raw()
+            ci, rep = self.unpack(p)
+            return api.results_to_python(p.status, p.err_code, p.err_arg, p.offsets, ci, rep, p.n_bindings)
         r = self.schedule_raw()
         return api.results_to_python(r.status, r.err_code, r.err_arg, r.offsets, r.cluster_idx, r.replicas,
                                      r.n_bindings)

@@ -62,6 +62,25 @@ static int run_case(kp_engine* e, int config, uint64_t seed, uint32_t C, uint64_
       if (!same && bad++ < 3) fprintf(stderr, "config %d seed %llu binding %llu differs\n", config,
                                       (unsigned long long)seed, (unsigned long long)i);
     }
+    // the same batch in the packed result form, decoded by kp_results_unpack (the wide
+    // result's buffers are reused by this call, so it runs after the comparison above)
+    kp_results_packed p{};
+    if (kp_schedule_batch_packed(e, b, &p)) {
+      fprintf(stderr, "config %d: packed: engine error: %s\n", config, kp_last_error(e));
+      bad++;
+    } else {
+      std::vector<uint32_t> ci(p.n_targets + 1);
+      std::vector<int32_t> rp(p.n_targets + 1);
+      if (kp_results_unpack(&p, ci.data(), rp.data()) || p.n_bindings != nb) bad++;
+      for (uint64_t i = 0; i < nb && p.n_bindings == nb; i++) {
+        const bool same = p.status[i] == want->status[i] && p.err_code[i] == want->err_code[i] &&
+                          p.err_arg[i] == want->err_arg[i] &&
+                          targets_of(p.offsets, ci.data(), rp.data(), i) ==
+                              targets_of(want->offsets, want->cluster_idx, want->replicas, i);
+        if (!same && bad++ < 3) fprintf(stderr, "config %d seed %llu binding %llu differs (packed)\n", config,
+                                        (unsigned long long)seed, (unsigned long long)i);
+      }
+    }
     kpo_results_free(want);
     kpo_world_destroy(ow);
   }
