@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define KP_ABI_VERSION 15
+#define KP_ABI_VERSION 16
 
 /* ------------------------------------------------------------------------- */
 /* Object model                                                              */
@@ -504,6 +504,46 @@ int kp_batch_digest(const kp_batch* b, uint64_t* out);
 int kp_batch_create_keyed(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
                           const kp_binding_key* keys, uint64_t n_bindings, kp_pack_cache* cache,
                           kp_batch** out);
+
+/* ---- the other ReplicaEstimators' answers ------------------------------------------
+ * calAvailableReplicas (pkg/scheduler/core/util.go:57-110) asks every registered
+ * ReplicaEstimator and keeps, per cluster, the minimum of the answers that are not
+ * UnauthenticReplica (-1) (mergeReplicaResults, util.go:157-170); only then does a leftover
+ * MaxInt32 become spec.Replicas. The multi-template path merges the same way
+ * (core/estimation.go:77-113). The engine computes the GeneralEstimator; with
+ * --enable-scheduler-estimator the caller hands in what the scheduler-estimator client
+ * answered.
+ *
+ * kp_estimates: the answers of the estimators other than the GeneralEstimator, already
+ * merged by the caller into one row per distinct request (min over those estimators of the
+ * answers that are not -1; -1 where none answered). Nothing is retained after the call. */
+typedef struct kp_estimates {
+  uint32_t n_rows;
+  uint64_t n_clusters;   /* must equal the snapshot's cluster count */
+  const int32_t* rows;   /* n_rows * n_clusters, caller cluster order; -1 = UnauthenticReplica */
+  const int32_t* row_of; /* n_bindings entries: the binding's row, or -1 for none */
+} kp_estimates;
+/* kp_batch_create (keys and cache NULL) or kp_batch_create_keyed (both given) with
+ * estimates. A binding with row r schedules over min(general(c), rows[r][c]) where
+ * rows[r][c] != -1 and over general(c) elsewhere, MaxInt32 then becoming spec.Replicas; a
+ * binding that takes MaxAvailableComponentSets (gate on, cluster spread [1,1]) is merged
+ * the same way; a non-workload binding (replicas == 0, no components) calls no estimator
+ * (util.go:69-73) and ignores its row. Every schedule call on the batch uses the rows
+ * (kp_schedule_batch, _submit / _collect and the packed forms). A binding's estimator class
+ * is (request, row): a packed record (kp_pack_cache) keeps the request alone, so the keys'
+ * records are reused from cycle to cycle while the rows change. est == NULL or n_rows == 0:
+ * the batch is byte for byte the one kp_batch_create / _keyed makes (equal
+ * kp_batch_digest). KP_EINVAL (kp_last_error says which) when n_clusters differs from the
+ * snapshot's cluster count, a row_of entry is outside -1..n_rows-1, or a row value is
+ * below -1.
+ * The per-pair entry points on such a batch (kp_max_available_replicas, kp_filter_*,
+ * kp_score_batch) keep answering for the in-tree set only: kp_max_available_replicas is
+ * the GeneralEstimator's answer, not the merged one. kp_schedule_affinities and kp_multi_*
+ * do not take estimates. */
+int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
+                              const kp_binding_key* keys /* may be NULL */, uint64_t n_bindings,
+                              kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
+                              kp_batch** out);
 
 /* genericScheduler.Schedule for every binding of the batch. */
 int kp_schedule_batch(kp_engine* e, kp_batch* b, kp_results* out);

@@ -191,6 +191,23 @@ class kp_pack_cache_stats(C.Structure):
     _fields_ = [("hits", u64), ("misses", u64), ("entries", u64), ("last_hits", u64)]
 
 
+class kp_estimates(C.Structure):
+    _fields_ = [("n_rows", u32), ("n_clusters", u64), ("rows", C.POINTER(i32)), ("row_of", C.POINTER(i32))]
+
+
+def estimates(rows, row_of):
+    """kp_estimates over `rows` (int32 [R, C]: the other estimators' merged answers, caller
+    cluster order, -1 = no answer) and `row_of` (each binding's row, -1 for none). Returns
+    the struct and the arrays it points into (keep them alive for the call)."""
+    import numpy as np
+    r = np.ascontiguousarray(rows, dtype=np.int32)
+    if r.ndim != 2:
+        raise ValueError("estimates: rows must be a 2-D int32 array [rows, clusters]")
+    ro = np.ascontiguousarray(row_of, dtype=np.int32).reshape(-1)
+    e = kp_estimates(r.shape[0], r.shape[1], r.ctypes.data_as(C.POINTER(i32)), ro.ctypes.data_as(C.POINTER(i32)))
+    return e, (r, ro)
+
+
 def binding_keys(bindings, n, generations):
     """kp_binding_key per binding: its uid (kp_binding.uid, shared, not copied) and the
     given metadata.generation."""

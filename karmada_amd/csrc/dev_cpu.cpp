@@ -272,6 +272,14 @@ int rows_from_class(stream_t, const SnapView& s, const BatchView& bv, const int3
   return 0;
 }
 
+int est_extra(stream_t, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
+              const int32_t* extra, int32_t* rows) {
+  grid(n, 0, [&](int blk, unsigned char* sm) {
+    body_est_extra(CpuBlk{(int64_t*)sm}, blk, 0, 1, Cp, list, bcls, cls_est, extra, rows);
+  });
+  return 0;
+}
+
 int grades(stream_t, const GradesArgs& A) {
   for (uint64_t i = 0; i < A.n; i++) body_grades(A, i);
   return 0;

@@ -413,6 +413,12 @@ struct kp_batch {
   bool est_single = false;
   std::vector<int32_t> l_cls_full, l_cls_single;
   int32_t *d_cls_full = nullptr, *d_cls_single = nullptr;
+  // The other estimators' answers (kp_batch_create_estimates; all empty / null for a batch
+  // without them, which allocates, uploads and launches nothing for it): cls_est[class] =
+  // the class's row of d_est_rows ([n_rows][Cp], by cluster rank, -1 in the padding), -1
+  // for none; l_est_cls: the classes that have one (k_est_extra's list in bits mode).
+  std::vector<int32_t> cls_est, l_est_cls;
+  int32_t *d_cls_est = nullptr, *d_est_cls = nullptr, *d_est_rows = nullptr;
   // component-set classes (BF_SETS): class id and resolved component list of each;
   // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
   // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)
@@ -2717,8 +2723,11 @@ static inline uint64_t cache_key(const kp_binding_key& k) {
   return h ? h : 1;
 }
 
+// row_of (kp_estimates, or null): each binding's row of the other estimators' answers; a
+// workload binding's estimator class is then (request key, row), the row appended to the
+// class key after the record lookup, so a cached record keeps the request key alone.
 bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* bt, const kp_binding_key* keys = nullptr,
-                   kp_pack_cache* cache = nullptr) {
+                   kp_pack_cache* cache = nullptr, const int32_t* row_of = nullptr) {
   int T = host_cpus();
   if (const char* v = getenv("KP_PACK_THREADS")) T = atoi(v);
   T = std::max(1, std::min(T, n / 4096));
@@ -2904,10 +2913,11 @@ bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* 
                         -(int32_t)to0, -(int32_t)pr0, -(int32_t)in0);
           newrecs[(size_t)k * kCacheShards + ck % kCacheShards].push_back(r);
         }
-        if (nonworkload) {
+        if (nonworkload) {  // (calls no estimator: its row, if any, is ignored)
           bt->bcls[i] = -1;
           continue;
         }
+        if (row_of) key.append((const char*)&row_of[i], 4);
         auto it = ids.find(key);
         if (it == ids.end()) {
           it = ids.emplace(key, (int32_t)tkeys[t].size()).first;
@@ -2952,6 +2962,7 @@ bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* 
   // global class ids (1-based; 0 = non-workload): the threads' keys in thread order
   SvMap<int32_t> gid;
   bt->crep.assign(1, 0);
+  if (row_of) bt->cls_est.assign(1, -1);
   std::vector<std::vector<int32_t>> remaps(T);
   for (int t = 0; t < T; t++) {
     std::vector<int32_t>& remap = remaps[t];
@@ -2962,6 +2973,12 @@ bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* 
       if ((size_t)it->second == bt->crep.size()) {
         bt->crep.push_back(-1);
         const std::string& key = tkeys[t][j];
+        if (row_of) {  // the key's last four bytes
+          int32_t r;
+          memcpy(&r, key.data() + key.size() - 4, 4);
+          bt->cls_est.push_back(r);
+          if (r >= 0) bt->l_est_cls.push_back(it->second);
+        }
         if (!key.empty() && key[0] == 'S') {  // component-set class: its rows come from k_sets_rows
           SetsArgs A;
           memcpy(&A, key.data() + 1, sizeof(A));
@@ -3069,7 +3086,13 @@ static int64_t order_amort() {  // (read per batch: tests switch it)
 }
 
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
-                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out);
+                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
+                             const kp_estimates* est = nullptr);
+int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
+                              uint64_t n, kp_pack_cache* cache, const kp_estimates* est, kp_batch** out) {
+  if (cache && n && !keys) return KP_EINVAL;  // (as kp_batch_create_keyed)
+  return batch_create_impl(e, sc, bindings, n, cache ? keys : nullptr, cache, out, est);
+}
 int kp_batch_create(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n, kp_batch** out) {
   return batch_create_impl(e, sc, bindings, n, nullptr, nullptr, out);
 }
@@ -3117,11 +3140,43 @@ int kp_pack_cache_get_stats(const kp_pack_cache* c, kp_pack_cache_stats* out) {
   return KP_OK;
 }
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
-                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out) {
+                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
+                             const kp_estimates* est) {
   if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
   if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
   (void)dev::set_device(e->device);
   kp_snapshot* s = const_cast<kp_snapshot*>(sc);
+  // The other estimators' rows (kp_estimates), checked and brought into rank order with the
+  // device rows' padding (-1: no answer) before anything is packed; none: est stays null.
+  std::vector<int32_t> est_rows;
+  if (est && est->n_rows == 0) est = nullptr;
+  if (est) {
+    auto bad = [&](std::string why) {
+      e->err = "kp_batch_create_estimates: " + why;
+      return KP_EINVAL;
+    };
+    if (est->n_clusters != (uint64_t)s->C)
+      return bad("n_clusters is " + std::to_string(est->n_clusters) + ", the snapshot holds " + std::to_string(s->C) +
+                 " clusters");
+    if (!est->rows || (n && !est->row_of)) return bad("rows or row_of is null");
+    if (est->n_rows > (uint32_t)INT32_MAX) return bad("more than 2^31 - 1 rows");
+    for (uint64_t i = 0; i < n; i++)
+      if (est->row_of[i] < -1 || est->row_of[i] >= (int64_t)est->n_rows)
+        return bad("row_of[" + std::to_string(i) + "] = " + std::to_string(est->row_of[i]) + " is outside -1.." +
+                   std::to_string((int64_t)est->n_rows - 1));
+    est_rows.assign((size_t)est->n_rows * s->Cp, -1);
+    for (uint32_t r = 0; r < est->n_rows; r++) {
+      const int32_t* src = est->rows + (size_t)r * s->C;
+      int32_t* dst = est_rows.data() + (size_t)r * s->Cp;
+      for (int k = 0; k < s->C; k++) {
+        const int32_t v = src[s->perm[k]];
+        if (v < -1)
+          return bad("rows[" + std::to_string(r) + "][" + std::to_string(s->perm[k]) + "] = " + std::to_string(v) +
+                     " is below -1 (UnauthenticReplica)");
+        dst[k] = v;
+      }
+    }
+  }
   auto* bt = new kp_batch();
   std::unique_ptr<kp_batch> guard(bt);
   bt->snap = s;
@@ -3135,7 +3190,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
                  " has n_components > 0 but no components (the MultiplePodTemplatesScheduling gate reads them)";
         return KP_EINVAL;
       }
-  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache)) {
+  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache, est ? est->row_of : nullptr)) {
     e->err = bt->err.empty() ? "batch pools exceed 2^31 entries" : bt->err;
     return KP_ENOTSUP;
   }
@@ -3361,7 +3416,11 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
       bt->sets_cls.empty()) {
     std::vector<int32_t> cnt(bt->crep.size(), 0);
     for (uint64_t i = 0; i < n; i++) cnt[(size_t)std::max(0, bt->bcls[i])]++;
-    for (size_t g = 0; g < bt->crep.size(); g++) (g > 0 && cnt[g] == 1 ? bt->l_cls_single : bt->l_cls_full).push_back((int32_t)g);
+    // (a class with a row of the other estimators' answers keeps its whole row: k_est_extra
+    // merges it before ev[5], the feasible-only rows are written after)
+    auto has_est = [&](size_t g) { return !bt->cls_est.empty() && bt->cls_est[g] >= 0; };
+    for (size_t g = 0; g < bt->crep.size(); g++)
+      (g > 0 && cnt[g] == 1 && !has_est(g) ? bt->l_cls_single : bt->l_cls_full).push_back((int32_t)g);
     bt->est_single = !bt->l_cls_single.empty();
     if (bt->est_single) {
       a.add(&bt->d_cls_full, bt->l_cls_full.size());
@@ -3396,6 +3455,11 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     a.add(&bt->d_sets_ovf, bt->sets_cls.size());
     a.add(&bt->d_sets_list, bt->l_sets.size());
   }
+  if (!bt->l_est_cls.empty()) {
+    a.add(&bt->d_cls_est, bt->cls_est.size());
+    a.add(&bt->d_est_cls, bt->l_est_cls.size());
+    a.add(&bt->d_est_rows, est_rows.size());
+  }
   const auto tp1 = std::chrono::steady_clock::now();
   HIPCHK(a.alloc());
   bt->h_kargs = (KArgs*)pinned_get(sizeof(KArgs) * kArgSlots, &bt->h_kargs_bytes);
@@ -3428,6 +3492,14 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   if (bt->est_single) {
     HIPCHK(up(bt->d_cls_full, bt->l_cls_full.data(), 4 * bt->l_cls_full.size()));
     HIPCHK(up(bt->d_cls_single, bt->l_cls_single.data(), 4 * bt->l_cls_single.size()));
+  }
+  if (!bt->l_est_cls.empty()) {
+    HIPCHK(up(bt->d_cls_est, bt->cls_est.data(), 4 * bt->cls_est.size()));
+    HIPCHK(up(bt->d_est_cls, bt->l_est_cls.data(), 4 * bt->l_est_cls.size()));
+    HIPCHK(up(bt->d_est_rows, est_rows.data(), 4 * est_rows.size()));
+    if (getenv("KP_PACK_TIMING"))
+      fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
+              bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + est_rows.size()));
   }
   HIPCHK(up(bt->d_all, bt->l_all.data(), 4 * bt->l_all.size()));
   bt->l_all_cls.resize(bt->l_all.size());
@@ -3730,6 +3802,12 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
     KPROF(sp, est_class_name(fast), n_full, -1,
           dev::est_class(sp, s->view, bt->view, bt->d_crep, n_full, bt->cls_rows, fast, single ? bt->d_cls_full : nullptr));
     if (int rc = sets_rows()) return rc;
+    // the other estimators' answers merged into their classes' raw rows: every reader
+    // below (class orders, the select kernels, k_slow) then sees merged rows
+    if (!bt->l_est_cls.empty())
+      KPROF(sp, "k_est_extra", bt->l_est_cls.size(), -1,
+            dev::est_extra(sp, s->Cp, bt->d_est_cls, (int)bt->l_est_cls.size(), nullptr, bt->d_cls_est, bt->d_est_rows,
+                           bt->cls_rows));
     HIPCHK(dev::event_record(e->ev[5], sp));  // every class row is written (k_class_order's input)
     KPROF(sp, "k_filter", B, -1, dev::filter(sp, s->view, bt->view, bt->fmask));
     if (single)  // the singleton classes' feasible entries, from the feasibility rows
@@ -3746,6 +3824,12 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
     KPROF(sp, "k_rows_from_class", bt->l_sets.size(), -1,
           dev::rows_from_class(sp, s->view, bt->view, bt->d_sets_list, (int)bt->l_sets.size(), bt->d_bcls,
                                bt->cls_rows, bt->fmask, bt->est));
+  // pair-row mode: the same merge over the rows of the bindings whose class has a row; the
+  // entries are cal_merge'd already (0 on infeasible clusters), and a GeneralEstimator
+  // answer is below MaxInt32, so the minimum is the reference's
+  if (!bits && !bt->l_est_cls.empty())
+    KPROF(sp, "k_est_extra", B, -1,
+          dev::est_extra(sp, s->Cp, nullptr, B, bt->d_bcls, bt->d_cls_est, bt->d_est_rows, bt->est));
   // SEL_ALL DynamicWeight / Aggregated over the deciding candidates (kp_top.h): the
   // class rows' orders first
   // the large slice's capacity, lowered until the slices fit the device's LDS

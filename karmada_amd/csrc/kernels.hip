@@ -413,6 +413,17 @@ extern "C" __global__ void __launch_bounds__(256) k_rows_from_class(SnapView s, 
 #else
 ;
 #endif
+// One row per blockIdx.x, gridDim.y workgroups along it (16 bytes per lane: coalesced).
+extern "C" __global__ void __launch_bounds__(256) k_est_extra(int Cp, const int32_t* list, const int32_t* bcls,
+                                                            const int32_t* cls_est, const int32_t* extra,
+                                                            int32_t* rows)
+#if KP_K(1)
+{
+  body_est_extra(GpuBlk{nullptr}, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y, Cp, list, bcls, cls_est, extra, rows);
+}
+#else
+;
+#endif
 extern "C" __global__ void __launch_bounds__(256) k_grades(GradesArgs A)
 #if KP_K(8)
 {
@@ -844,6 +855,15 @@ int rows_from_class(stream_t st, const SnapView& s, const BatchView& bv, const i
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_rows_from_class, dim3(n), dim3(256), 0, (hipStream_t)st, s, bv, list, bcls, cls_rows, fmask,
                      est);
+  return chk(hipGetLastError());
+}
+
+int est_extra(stream_t st, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
+              const int32_t* extra, int32_t* rows) {
+  if (n <= 0) return 0;
+  // (a workgroup covers 1024 entries a step; at most 64 along a row, which then stride)
+  const int parts = std::max(1, std::min(64, (Cp / 4 + 255) / 256));
+  hipLaunchKernelGGL(k_est_extra, dim3(n, parts), dim3(256), 0, (hipStream_t)st, Cp, list, bcls, cls_est, extra, rows);
   return chk(hipGetLastError());
 }
 

@@ -103,6 +103,12 @@ int sets_rows(stream_t st, const SnapView& s, const SetsArgs* A, const int64_t* 
 // (cal_merge_bf with spec.Replicas on feasible clusters, 0 elsewhere, as pair_eval writes).
 int rows_from_class(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* list, int n,
                     const int32_t* bcls, const int32_t* cls_rows, const uint64_t* fmask, int32_t* est);
+// kp_batch_create_estimates: the other estimators' answers merged into n estimate rows
+// (body_est_extra): row d = list[i] (i when list is null) of rows[..][Cp], its class
+// bcls[d] (d when bcls is null), that class's row cls_est[class] of extra[..][Cp] (rank
+// order, -1 = no answer; negative cls_est: the row is left alone).
+int est_extra(stream_t st, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
+              const int32_t* extra, int32_t* rows);
 // kp_model_grades: A.counts[grade] += 1 per node (body_grades); A's arrays in device memory.
 int grades(stream_t st, const GradesArgs& A);
 // kp_node_max_replicas: *A.sum += int32 sum of node_replicas over the nodes (wrapping).

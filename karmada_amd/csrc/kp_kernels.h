@@ -317,6 +317,39 @@ KP_FI void body_rows_from_class(const BLK& B, int blk, const SnapView& s, const 
   for (int c = B.tid(); c < s.C; c += B.nth()) row[c] = mask_test(fr, c) ? cal_merge_bf(rep, cr[c]) : 0;
 }
 
+// mergeReplicaResults (core/util.go:157-170) of one more estimator's answer x into a row
+// entry g: x == -1 (UnauthenticReplica) leaves g, else the smaller of the two; a g of -1
+// (no answer so far) takes x.
+KP_HD inline int32_t est_extra_merge(int32_t g, int32_t x) { return x == -1 ? g : (g == -1 || x < g ? x : g); }
+struct alignas(16) EstQuad {
+  int32_t v[4];
+};
+
+// The other estimators' answers merged into estimate rows (kp_batch_create_estimates). Item
+// blk is row d = list[blk] (blk without a list) of `rows` ([..][Cp]); its class is bcls[d]
+// (d without bcls) and that class's extra row cls_est[class] of `extra` ([..][Cp], by
+// cluster rank, -1 in the padding and wherever no estimator answered), none when negative.
+// Bits mode: the listed classes' raw rows of cls_rows; pair-row mode: every binding's
+// cal_merge'd row (0 on infeasible clusters, so the minimum keeps them 0). Four entries
+// per thread and step (rows and Cp are 16-byte multiples), part `part` of `parts` per row;
+// a -1 leaves its entry as it is, the padding [C, Cp) with it.
+template <class BLK>
+KP_FI void body_est_extra(const BLK& B, int blk, int part, int parts, int Cp, const int32_t* list,
+                          const int32_t* bcls, const int32_t* cls_est, const int32_t* extra, int32_t* rows) {
+  const int d = list ? list[blk] : blk;
+  const int32_t r = cls_est[bcls ? bcls[d] : d];
+  if (r < 0) return;
+  EstQuad* row = (EstQuad*)(rows + (size_t)d * Cp);
+  const EstQuad* x = (const EstQuad*)(extra + (size_t)r * Cp);
+  for (int q = part * B.nth() + B.tid(); q < Cp / 4; q += parts * B.nth()) {
+    EstQuad g = row[q];
+    const EstQuad e = x[q];
+KP_UNROLL
+    for (int j = 0; j < 4; j++) g.v[j] = est_extra_merge(g.v[j], e.v[j]);
+    row[q] = g;
+  }
+}
+
 // Pair stage for binding list[b0 + blk] (b0 + blk without a list): each wave evaluates 64 consecutive clusters
 // (coalesced SoA columns), stores their feasibility as one u64 word and
 // calAvailableReplicas per cluster. est_mode 1: raw GeneralEstimator answers for

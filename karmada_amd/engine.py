@@ -25,7 +25,7 @@ from karmada_amd import api
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libkp.so")
-KP_ABI_VERSION = 15
+KP_ABI_VERSION = 16
 
 _LIBS = {}
 
@@ -33,7 +33,7 @@ _LIBS = {}
 EXPORTS = (
     "kp_abi_version", "kp_engine_create", "kp_engine_destroy", "kp_last_error", "kp_snapshot_create",
     "kp_snapshot_destroy", "kp_snapshot_export", "kp_snapshot_import", "kp_snapshot_update", "kp_batch_create",
-    "kp_batch_destroy", "kp_batch_create_keyed", "kp_batch_digest", "kp_pack_cache_create", "kp_pack_cache_destroy",
+    "kp_batch_destroy", "kp_batch_create_keyed", "kp_batch_create_estimates", "kp_batch_digest", "kp_pack_cache_create", "kp_pack_cache_destroy",
     "kp_pack_cache_get_stats",
     "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
     "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
@@ -78,6 +78,8 @@ def load_library(path: str = LIB_PATH):
     L.kp_pack_cache_get_stats.argtypes = [vp, C.POINTER(api.kp_pack_cache_stats)]
     L.kp_batch_create_keyed.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.POINTER(api.kp_binding_key), C.c_uint64,
                                         vp, C.POINTER(vp)]
+    L.kp_batch_create_estimates.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.POINTER(api.kp_binding_key),
+                                            C.c_uint64, vp, C.POINTER(api.kp_estimates), C.POINTER(vp)]
     L.kp_schedule_batch.argtypes = [vp, vp, C.POINTER(api.kp_results)]
     L.kp_schedule_batch_submit.argtypes = [vp, vp]
     L.kp_schedule_batch_collect.argtypes = [vp, vp, C.POINTER(api.kp_results)]
@@ -340,10 +342,13 @@ class PackCache:
 class Batch:
     """A batch of ResourceBindings packed against one snapshot (kp_batch). With `cache`
     and `keys` ((uid, generation) per binding, api.binding_keys) it is created through
-    kp_batch_create_keyed: bindings whose record the cache holds skip packing."""
+    kp_batch_create_keyed: bindings whose record the cache holds skip packing. With
+    `estimates` = (rows, row_of) it is created through kp_batch_create_estimates: rows is an
+    int32 array [R, C] of the other estimators' merged answers (caller cluster order, -1 =
+    no answer), row_of each binding's row (-1 for none)."""
 
     def __init__(self, snap: Snapshot, bindings: Sequence[dict] = (), structs=None, cache: "PackCache" = None,
-                 keys=None, generations: Sequence[int] = None):
+                 keys=None, generations: Sequence[int] = None, estimates=None):
         self.snap = snap
         eng = snap.engine
         if structs is None:
@@ -354,9 +359,18 @@ class Batch:
             ba, n = structs
         self.n = n
         h = C.c_void_p()
-        if cache is not None:
-            if keys is None:  # (uid from each binding, metadata.generation given)
-                keys = api.binding_keys(ba, n, generations if generations is not None else [0] * n)
+        if cache is not None and keys is None:  # (uid from each binding, metadata.generation given)
+            keys = api.binding_keys(ba, n, generations if generations is not None else [0] * n)
+        if estimates is not None:
+            rows, row_of = estimates
+            if len(row_of) != n:
+                raise ValueError(f"estimates: row_of has {len(row_of)} entries for {n} bindings")
+            est, self._est = api.estimates(rows, row_of)
+            self._keys = keys if cache is not None else None
+            eng._check(eng.L.kp_batch_create_estimates(eng.h, snap.h, ba, self._keys, n,
+                                                       cache.h if cache is not None else None, C.byref(est),
+                                                       C.byref(h)), "kp_batch_create_estimates")
+        elif cache is not None:
             self._keys = keys
             eng._check(eng.L.kp_batch_create_keyed(eng.h, snap.h, ba, keys, n, cache.h, C.byref(h)),
                        "kp_batch_create_keyed")

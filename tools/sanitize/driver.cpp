@@ -81,6 +81,31 @@ static int run_case(kp_engine* e, int config, uint64_t seed, uint32_t C, uint64_
                                         (unsigned long long)seed, (unsigned long long)i);
       }
     }
+    // the same bindings through kp_batch_create_estimates with rows that change nothing
+    // (MaxInt32: the general answer is the minimum; -1: no answer), every third binding
+    // without a row: the class split, the row upload and k_est_extra run, the placements stay
+    {
+      std::vector<int32_t> rows(2 * nc, INT32_MAX), row_of(nb);
+      std::fill(rows.begin() + (long)nc, rows.end(), -1);
+      for (uint64_t i = 0; i < nb; i++) row_of[i] = (int32_t)(i % 3) - 1;
+      const kp_estimates est{2, nc, rows.data(), row_of.data()};
+      kp_batch* be = nullptr;
+      kp_results re{};
+      if (kp_batch_create_estimates(e, s, bs, nullptr, nb, nullptr, &est, &be) || kp_schedule_batch(e, be, &re)) {
+        fprintf(stderr, "config %d: estimates: engine error: %s\n", config, kp_last_error(e));
+        bad++;
+      } else {
+        for (uint64_t i = 0; i < nb; i++) {
+          const bool same = re.status[i] == want->status[i] && re.err_code[i] == want->err_code[i] &&
+                            re.err_arg[i] == want->err_arg[i] &&
+                            targets_of(re.offsets, re.cluster_idx, re.replicas, i) ==
+                                targets_of(want->offsets, want->cluster_idx, want->replicas, i);
+          if (!same && bad++ < 3) fprintf(stderr, "config %d seed %llu binding %llu differs (estimates)\n", config,
+                                          (unsigned long long)seed, (unsigned long long)i);
+        }
+      }
+      if (be) kp_batch_destroy(be);
+    }
     kpo_results_free(want);
     kpo_world_destroy(ow);
   }
