@@ -127,7 +127,10 @@ constexpr int kFilterWaves = 4;
 extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_filter(SnapView s, BatchView bv, uint64_t* fmask)
 #if KP_K(1)
 {
-  const int b = (int)(blockIdx.x * kFilterWaves + (threadIdx.x >> 6));
+  // (the wave index through a scalar register: the compiler cannot see that
+  // threadIdx.x >> 6 is the same in every lane, and would walk the binding's header
+  // and predicate pools with vector loads)
+  const int b = (int)(blockIdx.x * kFilterWaves) + kp_uniform((int)(threadIdx.x >> 6));
   if (b >= bv.B) return;  // wave-uniform
   body_filter(GpuBlk{nullptr}, b, s, bv, fmask);
 }

@@ -141,19 +141,52 @@ KP_HD inline uint64_t filter_word(const SnapView& s, const BatchView& bv, const 
   return m;
 }
 
+// taints_tolerated (kp_algo.h) of taints [t0, t1) with the binding's first kTolRegs
+// tolerations in tr[] (loaded once per binding) and the rest read from the pool.
+constexpr int kTolRegs = 4;
+KP_FI bool taints_tolerated_regs(const SnapView& s, const BatchView& bv, const BindHdr& h, const Tol (&tr)[kTolRegs],
+                                 int t0, int t1) {
+  for (int t = t0; t < t1; t++) {
+    const int32_t k = s.taint_key[t], v = s.taint_val[t], e = s.taint_eff[t];
+    auto hit = [&](const Tol& tl) {
+      return (tl.eff == EFF_ANY || tl.eff == e) && (tl.key < 0 || tl.key == k) && (tl.op == TOL_EXISTS || tl.val == v);
+    };
+    bool tol = false;
+KP_UNROLL
+    for (int j = 0; j < kTolRegs; j++) tol = tol | (j < h.tol_cnt && hit(tr[j]));
+    for (int j = kTolRegs; j < h.tol_cnt && !tol; j++) tol = hit(kp_ldu(bv.tols + h.tol_off + j));
+    if (!tol) return false;
+  }
+  return true;
+}
+
 // k_filter: binding b's feasibility row fmask[b][0, W), by the calling wave (one
-// lane per word; on the host build one "lane" walks every word).
+// lane per word; on the host build one "lane" walks every word). b is wave-uniform
+// (the kernel passes it through kp_uniform): the header and everything filter_word
+// walks from it (program ids, Progs, Instrs, values, table probes, row ids) then go
+// through scalar loads and scalar registers, and only the bits words are vector loads.
 template <class BLK>
 KP_FI void body_filter(const BLK& B, int b, const SnapView& s, const BatchView& bv, uint64_t* fmask) {
-  const BindHdr h = bv.hdr[b];
+  const BindHdr h = kp_ldu(bv.hdr + b);
   const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
   uint64_t tolm = 0;  // TaintToleration once per distinct taint list (n_tsets <= kTsetRowsMax)
-  if (h.enabled & 2)
+  if (h.enabled & 2) {
+    // the binding's tolerations once, ahead of the taint loop
+    Tol tr[kTolRegs];
+KP_UNROLL
+    for (int j = 0; j < kTolRegs; j++)
+      tr[j] = j < h.tol_cnt ? kp_ldu(bv.tols + h.tol_off + j) : Tol{0, 0, TOL_EQUAL, -1};
     for (int t0 = 0; t0 < s.n_tsets; t0 += ww) {
       const int t = t0 + lane;
-      const bool ok = t < s.n_tsets && taints_tolerated(s, bv, h, s.tset_rep[t]);
+      int tt0 = 0, tt1 = 0;
+      if (t < s.n_tsets) {
+        const int c = s.tset_rep[t];
+        tt0 = s.taint_off[c], tt1 = s.taint_off[c + 1];
+      }
+      const bool ok = t < s.n_tsets && taints_tolerated_regs(s, bv, h, tr, tt0, tt1);
       tolm |= B.wballot(ok) << t0;
     }
+  }
   uint64_t* row = fmask + (size_t)b * s.W;
   for (int w0 = 0; w0 < s.W; w0 += ww) {
     const int w = w0 + lane;

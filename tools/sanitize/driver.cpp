@@ -6,10 +6,16 @@
 // UndefinedBehaviorSanitizer (tools/sanitize/Makefile). It schedules seeded
 // universes of every workload with KP_CPUSIM_THREADS concurrent "workgroups" and
 // checks each binding against the oracle (status, error, argument, multiset of
-// targets). Exit code 0 = no mismatch (the sanitizers abort on their own findings).
+// targets). A hand-built batch (run_filter_shapes) adds the predicate shapes the
+// synthetic universes lack (several affinity terms, a list of more than 64 values,
+// more than four tolerations, spec.Clusters members with eviction tasks) through
+// the bitset filter, every (binding, cluster) pair against the oracle's filter.
+// Exit code 0 = no mismatch (the sanitizers abort on their own findings).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -117,6 +123,207 @@ static int run_case(kp_engine* e, int config, uint64_t seed, uint32_t C, uint64_
   return bad ? 1 : 0;
 }
 
+// ---- hand-built filter shapes ---------------------------------------------------
+// Owns every string and array the kp_* views below point into.
+struct Arena {
+  std::deque<std::string> strs;
+  std::deque<std::vector<kp_str>> lists;
+  std::deque<std::vector<kp_requirement>> reqs;
+  std::deque<std::vector<kp_cluster_affinity>> affs;
+  std::deque<std::vector<kp_toleration>> tols;
+  std::deque<std::vector<kp_label>> labels;
+  std::deque<std::vector<kp_taint>> taints;
+  std::deque<std::vector<kp_api_enablement>> apis;
+  std::deque<std::vector<kp_target_cluster>> tgts;
+  std::deque<std::vector<kp_affinity_term>> terms;
+  kp_str s(const std::string& v) {
+    strs.push_back(v);
+    return kp_str{strs.back().data(), (uint32_t)strs.back().size()};
+  }
+  const kp_str* list(const std::vector<std::string>& v) {
+    lists.emplace_back();
+    for (auto& x : v) lists.back().push_back(s(x));
+    return lists.back().data();
+  }
+  kp_requirement req(const std::string& key, const std::string& op, const std::vector<std::string>& v = {}) {
+    return kp_requirement{s(key), s(op), v.empty() ? nullptr : list(v), (uint32_t)v.size()};
+  }
+  kp_cluster_affinity aff(const std::vector<kp_requirement>& lbl, const std::vector<kp_requirement>& fld,
+                          const std::vector<std::string>& names = {}, const std::vector<std::string>& excl = {}) {
+    kp_cluster_affinity a{};
+    if (!lbl.empty()) {
+      reqs.push_back(lbl);
+      a.has_label_selector = 1;
+      a.match_expressions = reqs.back().data();
+      a.n_match_expressions = (uint32_t)lbl.size();
+    }
+    if (!fld.empty()) {
+      reqs.push_back(fld);
+      a.has_field_selector = 1;
+      a.field_expressions = reqs.back().data();
+      a.n_field_expressions = (uint32_t)fld.size();
+    }
+    if (!names.empty()) a.cluster_names = list(names), a.n_cluster_names = (uint32_t)names.size();
+    if (!excl.empty()) a.exclude_clusters = list(excl), a.n_exclude_clusters = (uint32_t)excl.size();
+    return a;
+  }
+};
+
+static int run_filter_shapes(kp_engine* e) {
+  Arena A;
+  const int C = 131;  // three words, the last one partial
+  auto sh = [](int i) { return "s" + std::to_string(i); };
+  std::vector<std::string> names;
+  std::vector<kp_cluster> cl(C);
+  for (int i = 0; i < C; i++) {
+    kp_cluster& c = cl[i];
+    c = kp_cluster{};
+    char nm[16];
+    snprintf(nm, sizeof nm, "m-%04d", i);
+    names.push_back(nm);
+    c.name = A.s(nm);
+    c.deleting = i % 37 == 36;
+    A.labels.emplace_back();
+    A.labels.back().push_back({A.s("shard"), A.s(sh(i % 97))});
+    if (i % 5) A.labels.back().push_back({A.s("env"), A.s(std::string(1, (char)('a' + i % 4)))});
+    c.labels = A.labels.back().data();
+    c.n_labels = (uint32_t)A.labels.back().size();
+    if (i % 7) c.provider = A.s(i % 2 ? "aws" : "12");
+    if (i % 6) c.region = A.s(i % 3 ? "r1" : "100");
+    if (i % 4) {
+      c.zones = A.list({i % 2 ? "z1" : "z2", "z3"});
+      c.n_zones = 2;
+    }
+    if (i < 40) {  // 40 taint lists of their own, plus the empty one
+      A.taints.emplace_back();
+      A.taints.back().push_back({A.s("k" + std::to_string(i)), A.s("v"), A.s("NoSchedule")});
+      if (i % 3 == 0) A.taints.back().push_back({A.s("maint"), A.s("x"), A.s("NoExecute")});
+      c.taints = A.taints.back().data();
+      c.n_taints = (uint32_t)A.taints.back().size();
+    }
+    A.apis.emplace_back();
+    if (i % 9) A.apis.back().push_back({A.s("apps/v1"), A.s("Deployment")});
+    c.api_enablements = A.apis.back().data();
+    c.n_api_enablements = (uint32_t)A.apis.back().size();
+  }
+  auto shards = [&](int lo, int hi) {
+    std::vector<std::string> v;
+    for (int i = lo; i < hi; i++) v.push_back(sh(i));
+    return v;
+  };
+  auto tol = [&](const std::string& key, const std::string& op, const std::string& val, const std::string& eff) {
+    return kp_toleration{A.s(key), A.s(op), A.s(val), A.s(eff)};
+  };
+  std::vector<kp_binding> bs;
+  auto binding = [&]() -> kp_binding& {
+    bs.emplace_back();
+    kp_binding& b = bs.back();
+    b = kp_binding{};
+    b.uid = A.s("uid-" + std::to_string(bs.size()));
+    b.api_version = A.s("apps/v1");
+    b.kind = A.s("Deployment");
+    b.namespace_ = A.s("ns");
+    b.name = A.s("b" + std::to_string(bs.size()));
+    b.replicas = 3;
+    b.observed_affinity_name = A.s("t0");
+    return b;
+  };
+  auto terms = [&](kp_binding& b, const std::vector<kp_cluster_affinity>& affs) {  // term t0 + overflow terms
+    A.affs.emplace_back(affs.begin() + 1, affs.end());
+    A.terms.emplace_back(1, kp_affinity_term{A.s("t0"), affs[0], A.affs.back().data(), (uint32_t)affs.size() - 1});
+    b.cluster_affinities = A.terms.back().data();
+    b.n_cluster_affinities = 1;
+  };
+  auto one = [&](kp_binding& b, const kp_cluster_affinity& a) {
+    b.has_cluster_affinity = 1;
+    b.cluster_affinity = a;
+  };
+  auto tols = [&](kp_binding& b, const std::vector<kp_toleration>& t) {
+    A.tols.push_back(t);
+    b.tolerations = A.tols.back().data();
+    b.n_tolerations = (uint32_t)t.size();
+  };
+  const std::vector<kp_toleration> few = {tol("k1", "Exists", "", ""), tol("k2", "Equal", "v", "NoSchedule"),
+                                          tol("maint", "Equal", "x", "")};
+  // the matching tolerations behind more than four that match nothing (strings the snapshot knows)
+  std::vector<kp_toleration> many;
+  for (int j = 1; j <= 5; j++) many.push_back(tol(sh(j), "Exists", "", ""));
+  many.push_back(tol("k0", "Equal", "v", ""));
+  many.push_back(tol("maint", "Exists", "", ""));
+  many.push_back(tol("k3", "Exists", "", "NoExecute"));
+  std::vector<kp_toleration> lots;
+  for (int j = 0; j < 40; j += 2) lots.push_back(tol("k" + std::to_string(j), "Exists", "", ""));
+
+  binding();                                                          // no affinity, no toleration
+  one(binding(), A.aff({A.req("env", "In", {"a"})}, {}));             // one term, one value
+  one(binding(), A.aff({A.req("env", "NotIn", {"s5", "s6"})}, {}));   // values no cluster carries
+  {                                                                   // several terms, several instructions
+    kp_binding& b = binding();
+    terms(b, {A.aff({A.req("env", "In", {"a", "b"}), A.req("shard", "NotIn", shards(0, 7))}, {A.req("provider", "In", {"aws"})}),
+              A.aff({A.req("env", "DoesNotExist")}, {A.req("zone", "In", {"z1", "z3"}), A.req("region", "NotIn", {"r1"})}),
+              A.aff({A.req("shard", "In", shards(3, 9))}, {A.req("zone", "DoesNotExist")}),
+              A.aff({}, {A.req("region", "Exists"), A.req("provider", "Lt", {"50"})}, {}, {names[1], names[70], names[130]})});
+    tols(b, few);
+  }
+  {                                                                   // more than 64 values, mixed with names and Gt
+    kp_binding& b = binding();
+    one(b, A.aff({A.req("shard", "In", shards(10, 80)), A.req("env", "Exists")}, {A.req("provider", "Gt", {"6"})},
+                 std::vector<std::string>(names.begin(), names.begin() + 100)));
+    tols(b, many);
+  }
+  one(binding(), A.aff({A.req("shard", "NotIn", shards(0, 66))}, {}));
+  {                                                                   // 70 terms
+    kp_binding& b = binding();
+    std::vector<kp_cluster_affinity> t;
+    for (int j = 0; j < 70; j++) t.push_back(A.aff({A.req("shard", "In", {sh(j)})}, {}));
+    terms(b, t);
+    tols(b, lots);
+  }
+  tols(binding(), many);
+  tols(binding(), {tol("", "Exists", "", "NoSchedule")});
+  for (int k = 0; k < 2; k++) {  // spec.Clusters members failing APIEnablement and TaintToleration, eviction tasks
+    kp_binding& b = binding();
+    b.api_version = A.s("nope/v9");
+    b.kind = A.s("Thing");
+    A.tgts.emplace_back();
+    for (int i : {0, 1, 2, 9, 64, 130}) A.tgts.back().push_back({A.s(names[i]), 1});
+    b.clusters = A.tgts.back().data();
+    b.n_clusters = (uint32_t)A.tgts.back().size();
+    b.eviction_from = A.list({names[0], names[64]});
+    b.n_eviction_from = 2;
+    if (k) one(b, A.aff({A.req("shard", "NotIn", {"s1"})}, {})), tols(b, few);
+  }
+
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  kp_snapshot* s = nullptr;
+  kp_batch* b = nullptr;
+  const uint64_t nb = bs.size(), W = (C + 63) / 64;
+  std::vector<uint64_t> mask(nb * W);
+  int bad = 0;
+  uint64_t fit = 0;
+  if (kp_snapshot_create(e, cl.data(), C, &o, &s) || kp_batch_create(e, s, bs.data(), nb, &b) ||
+      kp_filter_batch(e, b, mask.data())) {
+    fprintf(stderr, "filter shapes: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  } else {
+    for (uint64_t i = 0; i < nb; i++)
+      for (int c = 0; c < C; c++) {
+        const bool got = (mask[i * W + (c >> 6)] >> (c & 63)) & 1;
+        const bool want = !cl[c].deleting && kpo_filter(&cl[c], &bs[i], &o) == 0;
+        fit += want;
+        if (got != want && bad++ < 5) fprintf(stderr, "filter shapes: binding %llu cluster %d: got %d want %d\n",
+                                              (unsigned long long)i, c, (int)got, (int)want);
+      }
+  }
+  if (b) kp_batch_destroy(b);
+  if (s) kp_snapshot_destroy(s);
+  printf("filter shapes: %llu bindings x %d clusters, %llu fitting pairs, %d mismatches\n", (unsigned long long)nb, C,
+         (unsigned long long)fit, bad);
+  return bad ? 1 : 0;
+}
+
 int main() {
   kp_engine* e = nullptr;
   if (kp_engine_create(0, &e)) return 2;
@@ -126,6 +333,7 @@ int main() {
       {7, 17, 200, 300, false}, {8, 4, 64, 150, false}, {9, 1, 150, 300, true}, {2, 2, 200, 200, false},
   };
   for (auto& c : cases) fails += run_case(e, std::get<0>(c), std::get<1>(c), std::get<2>(c), std::get<3>(c), std::get<4>(c));
+  fails += run_filter_shapes(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
