@@ -281,7 +281,9 @@ typedef struct kp_options {
    * RunScorePlugins (runtime/framework.go:93-170) run every registered plugin, so
    * the batch path, which computes the in-tree set only, would place differently:
    * kp_schedule_batch, kp_schedule_affinities and kp_multi_schedule return
-   * KP_ENOTSUP for a snapshot with n_out_of_tree_plugins > 0. The per-pair entry
+   * KP_ENOTSUP for a snapshot with n_out_of_tree_plugins > 0, except that a batch
+   * holding those plugins' filter verdicts (kp_batch_create_filters, filter-only
+   * plugins, n_plugins equal to this count) schedules. The per-pair entry
    * points (kp_filter_reasons, kp_score_batch, kp_max_available_replicas) still
    * answer for the in-tree set, for the framework to combine with the others. */
   uint32_t n_out_of_tree_plugins;
@@ -545,6 +547,48 @@ int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* s, const kp_bindi
                               kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
                               kp_batch** out);
 
+/* ---- out-of-tree filter plugins' verdicts ---------------------------------------------
+ * RunFilterPlugins (runtime/framework.go:93-105) is an AND over every registered filter
+ * plugin, and a plugin's verdict is per (binding, cluster). The engine computes the in-tree
+ * set; a scheduler that registers filter plugins of its own (app.WithPlugin) hands in their
+ * verdicts. Score plugins do not qualify: NormalizeScore runs over the
+ * feasible set, which is not known before the filter has run.
+ *
+ * kp_filter_answers: the out-of-tree filter plugins' verdicts, already ANDed by the caller
+ * into one row per distinct binding class. Nothing is retained after the call. */
+typedef struct kp_filter_answers {
+  uint32_t n_rows;
+  uint64_t n_clusters;   /* must equal the snapshot's cluster count */
+  const uint64_t* rows;  /* n_rows * ceil(n_clusters/64) words, caller cluster order, the layout
+                            of kp_filter_batch's out_mask: bit set = every out-of-tree filter
+                            plugin returned Success for this cluster */
+  const int32_t* row_of; /* n_bindings entries: the binding's row, or -1 (no plugin objected) */
+  uint32_t n_plugins;    /* how many registered out-of-tree plugins the rows fold in; the caller
+                            attests that all of them are filter-only (no Score) */
+} kp_filter_answers;
+/* kp_batch_create_estimates with filter answers. Cluster c is feasible for binding b iff the
+ * in-tree filter set passes it and bit c of b's row is set (a cluster named in spec.Clusters
+ * included); everything downstream (the FitError when nothing fits, locality, scale-down,
+ * spread, division) runs over that set. The schedule calls on the batch (kp_schedule_batch,
+ * _submit / _collect and the packed forms) run when flt->n_plugins equals the snapshot's
+ * n_out_of_tree_plugins (a batch without answers counts as 0) and return KP_ENOTSUP
+ * otherwise. kp_filter_batch returns the merged mask; kp_filter_reasons reports the in-tree
+ * reason where there is one and KP_REASON_OUT_OF_TREE where the in-tree set fits and the row
+ * rejects; kp_score_batch and kp_max_available_replicas are unchanged. The rows are not part
+ * of a binding's packed record or estimator class: a keyed batch reuses every record while
+ * the rows change. flt == NULL or n_rows == 0: the batch is byte for byte the one
+ * kp_batch_create_estimates makes (equal kp_batch_digest) and nothing new is allocated,
+ * uploaded or launched for it (a non-NULL flt with n_rows == 0 still states its n_plugins for
+ * the gate: plugins registered, none objected). Bits at or above n_clusters in a row's last word are ignored.
+ * KP_EINVAL (kp_last_error says which) when n_clusters differs from the snapshot's cluster
+ * count, rows is null, row_of is null with n_bindings > 0, a row_of entry is outside
+ * -1..n_rows-1, or n_rows > 0 with n_plugins == 0. kp_schedule_affinities and kp_multi_*
+ * take no answers. */
+int kp_batch_create_filters(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
+                            const kp_binding_key* keys /* may be NULL */, uint64_t n_bindings,
+                            kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
+                            const kp_filter_answers* flt /* may be NULL */, kp_batch** out);
+
 /* genericScheduler.Schedule for every binding of the batch. */
 int kp_schedule_batch(kp_engine* e, kp_batch* b, kp_results* out);
 /* kp_schedule_batch in two halves, for a caller that keeps batches in flight (a scheduler
@@ -608,6 +652,9 @@ enum {
   KP_REASON_SPREAD_REGION = 5,   /* spread_constraint.go:59 "cluster(s) did not have region property" */
   KP_REASON_SPREAD_ZONES = 6,    /* spread_constraint.go:61 "cluster(s) did not have zones property" */
   KP_REASON_EVICTION = 7,        /* cluster_eviction.go:53 "cluster(s) is in the process of eviction" */
+  KP_REASON_OUT_OF_TREE = 8,     /* the in-tree set fits, the batch's kp_filter_answers row rejects (the
+                                    plugin's own message is the caller's; the registry's plugin order is a
+                                    map iteration, so "in-tree first" is as faithful as any) */
   KP_REASON_DELETING = 255       /* generic_scheduler.go:138-142 (skipped) */
 };
 int kp_filter_reasons(kp_engine* e, kp_batch* b, uint32_t* out_reasons);

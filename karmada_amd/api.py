@@ -208,6 +208,50 @@ def estimates(rows, row_of):
     return e, (r, ro)
 
 
+class kp_filter_answers(C.Structure):
+    _fields_ = [("n_rows", u32), ("n_clusters", u64), ("rows", C.POINTER(u64)), ("row_of", C.POINTER(i32)),
+                ("n_plugins", u32)]
+
+
+def filter_rows(ok):
+    """Bool array [R, C] (True = every out-of-tree filter plugin returned Success) as the
+    uint64 words [R, ceil(C / 64)] of kp_filter_answers.rows (kp_filter_batch's layout)."""
+    import numpy as np
+    ok = np.asarray(ok, dtype=bool)
+    if ok.ndim != 2:
+        raise ValueError("filter_rows: ok must be a 2-D bool array [rows, clusters]")
+    r, c = ok.shape
+    bits = np.zeros((r, 64 * ((c + 63) // 64)), dtype=np.uint8)
+    bits[:, :c] = ok
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8").reshape(r, (c + 63) // 64)
+
+
+def filter_answers(rows, row_of, n_plugins, n_clusters=None):
+    """kp_filter_answers over `rows` (bool [R, C], or uint64 words [R, ceil(C / 64)] with
+    n_clusters given: bit set = every out-of-tree filter plugin passed the cluster, caller
+    cluster order), `row_of` (each binding's row, -1 for none) and the number of registered
+    out-of-tree plugins the rows fold in. Returns the struct and the arrays it points into
+    (keep them alive for the call)."""
+    import numpy as np
+    r = np.asarray(rows)
+    if r.ndim != 2:
+        raise ValueError("filter_answers: rows must be a 2-D array")
+    if r.dtype == np.uint64:
+        if n_clusters is None:
+            raise ValueError("filter_answers: rows given as words need n_clusters")
+        r = np.ascontiguousarray(r)
+    else:
+        if n_clusters is None:
+            n_clusters = r.shape[1]
+        r = filter_rows(r) if r.shape[0] else np.zeros((0, (n_clusters + 63) // 64), dtype=np.uint64)
+    if r.shape[1] != (n_clusters + 63) // 64:
+        raise ValueError(f"filter_answers: rows hold {r.shape[1]} words for {n_clusters} clusters")
+    ro = np.ascontiguousarray(row_of, dtype=np.int32).reshape(-1)
+    f = kp_filter_answers(r.shape[0], int(n_clusters), r.ctypes.data_as(C.POINTER(u64)),
+                          ro.ctypes.data_as(C.POINTER(i32)), int(n_plugins))
+    return f, (r, ro)
+
+
 def binding_keys(bindings, n, generations):
     """kp_binding_key per binding: its uid (kp_binding.uid, shared, not copied) and the
     given metadata.generation."""
@@ -253,6 +297,7 @@ STATUS_OK, STATUS_FIT_ERROR, STATUS_UNSCHEDULABLE, STATUS_ERROR = 0, 1, 2, 3
 # kp_filter_reasons codes (kp_api.h KP_REASON_*) and the Result reasons the plugins return
 REASON_FIT, REASON_API, REASON_TAINT, REASON_AFFINITY = 0, 1, 2, 3
 REASON_SPREAD_PROVIDER, REASON_SPREAD_REGION, REASON_SPREAD_ZONES, REASON_EVICTION = 4, 5, 6, 7
+REASON_OUT_OF_TREE = 8  # the batch's filter answers reject (the plugin's own text is the caller's)
 REASON_DELETING = 255
 REASON_TEXT = {
     REASON_API: "cluster(s) did not have the API resource",                              # api_enablement.go:77
@@ -272,9 +317,15 @@ def taint_string(t: dict) -> str:
     return "%s=%s:%s" % (t.get("key", ""), t.get("value", ""), t.get("effect", ""))
 
 
-def reason_text(code: int, cluster: dict) -> str:
-    """The Result reason of one kp_filter_reasons word for `cluster` (its dict form)."""
+def reason_text(code: int, cluster: dict, out_of_tree: str = None) -> str:
+    """The Result reason of one kp_filter_reasons word for `cluster` (its dict form).
+    out_of_tree: the text for REASON_OUT_OF_TREE, the rejecting plugin's own (the engine
+    sees the verdict only)."""
     kind, arg = code & 0xFF, code >> 8
+    if kind == REASON_OUT_OF_TREE:
+        if out_of_tree is None:
+            raise ValueError("reason_text: an out-of-tree verdict needs its plugin's reason text")
+        return out_of_tree
     if kind == REASON_TAINT:
         taints = [t for t in cluster.get("taints", []) if t.get("effect") in ("NoSchedule", "NoExecute")]
         return REASON_TEXT[kind] % taint_string(taints[arg])

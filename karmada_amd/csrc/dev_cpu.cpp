@@ -156,6 +156,22 @@ int filter(stream_t, const SnapView& s, const BatchView& bv, uint64_t* fmask) {
   return 0;
 }
 
+int filter_extra(stream_t, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, uint64_t* fmask,
+                 int32_t* est) {
+  grid(n, 0, [&](int i, unsigned char* sm) {
+    body_filter_extra(CpuBlk{(int64_t*)sm}, i, s.C, s.Cp, s.W, list, rows, fmask, est);
+  });
+  return 0;
+}
+
+int reasons_extra(stream_t, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, int b0,
+                  uint32_t* out) {
+  grid(n, 0, [&](int i, unsigned char* sm) {
+    body_reasons_extra(CpuBlk{(int64_t*)sm}, i, s.C, s.W, list, rows, b0, out);
+  });
+  return 0;
+}
+
 int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const SelectExtra& x) {
   switch (which) {
     case SEL_LAUNCH_ALL: {

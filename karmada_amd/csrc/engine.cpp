@@ -419,6 +419,16 @@ struct kp_batch {
   // for none; l_est_cls: the classes that have one (k_est_extra's list in bits mode).
   std::vector<int32_t> cls_est, l_est_cls;
   int32_t *d_cls_est = nullptr, *d_est_cls = nullptr, *d_est_rows = nullptr;
+  // The out-of-tree filter plugins' verdicts (kp_batch_create_filters; empty / null for a
+  // batch without rows, which allocates, uploads and launches nothing for them): l_flt =
+  // the bindings that have a row, (binding, row id) in binding order (k_filter_extra's
+  // list); d_flt_rows[n_rows][W] words by cluster rank, zero bits in the padding, fixed
+  // for the batch's lifetime. flt_plugins: how many registered plugins the answers fold
+  // in (the schedule calls' gate against kp_options.n_out_of_tree_plugins).
+  std::vector<FltPair> l_flt;
+  FltPair* d_flt_list = nullptr;
+  uint64_t* d_flt_rows = nullptr;
+  uint32_t flt_plugins = 0;
   // component-set classes (BF_SETS): class id and resolved component list of each;
   // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
   // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)
@@ -3087,7 +3097,13 @@ static int64_t order_amort() {  // (read per batch: tests switch it)
 
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
                              const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est = nullptr);
+                             const kp_estimates* est = nullptr, const kp_filter_answers* flt = nullptr);
+int kp_batch_create_filters(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
+                            uint64_t n, kp_pack_cache* cache, const kp_estimates* est, const kp_filter_answers* flt,
+                            kp_batch** out) {
+  if (cache && n && !keys) return KP_EINVAL;  // (as kp_batch_create_keyed)
+  return batch_create_impl(e, sc, bindings, n, cache ? keys : nullptr, cache, out, est, flt);
+}
 int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                               uint64_t n, kp_pack_cache* cache, const kp_estimates* est, kp_batch** out) {
   if (cache && n && !keys) return KP_EINVAL;  // (as kp_batch_create_keyed)
@@ -3141,7 +3157,7 @@ int kp_pack_cache_get_stats(const kp_pack_cache* c, kp_pack_cache_stats* out) {
 }
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
                              const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est) {
+                             const kp_estimates* est, const kp_filter_answers* flt) {
   if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
   if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
   (void)dev::set_device(e->device);
@@ -3177,11 +3193,52 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
       }
     }
   }
+  // The out-of-tree filter verdicts (kp_filter_answers), checked and brought into rank order
+  // (dev_row bit rank = caller_row bit perm[rank]; W words a row, zero bits in the padding,
+  // caller bits at or above C never read), and the bindings that have a row.
+  std::vector<uint64_t> flt_rows;
+  std::vector<FltPair> flt_list;
+  const uint32_t flt_plugins = flt ? flt->n_plugins : 0;
+  if (flt && flt->n_rows == 0) flt = nullptr;
+  if (flt) {
+    auto bad = [&](std::string why) {
+      e->err = "kp_batch_create_filters: " + why;
+      return KP_EINVAL;
+    };
+    if (flt->n_clusters != (uint64_t)s->C)
+      return bad("n_clusters is " + std::to_string(flt->n_clusters) + ", the snapshot holds " + std::to_string(s->C) +
+                 " clusters");
+    if (!flt->rows) return bad("rows is null");
+    if (n && !flt->row_of) return bad("row_of is null");
+    if (flt->n_plugins == 0) return bad("n_rows is " + std::to_string(flt->n_rows) + " with n_plugins == 0");
+    if (flt->n_rows > (uint32_t)INT32_MAX) return bad("more than 2^31 - 1 rows");
+    for (uint64_t i = 0; i < n; i++) {
+      const int32_t r = flt->row_of[i];
+      if (r < -1 || r >= (int64_t)flt->n_rows)
+        return bad("row_of[" + std::to_string(i) + "] = " + std::to_string(r) + " is outside -1.." +
+                   std::to_string((int64_t)flt->n_rows - 1));
+      if (r >= 0) flt_list.push_back(FltPair{(int32_t)i, r});
+    }
+    if (!flt_list.empty()) {  // (rows that no binding uses: nothing to merge)
+      const size_t Wc = ((size_t)s->C + 63) / 64;
+      flt_rows.assign((size_t)flt->n_rows * s->W, 0);
+      for (uint32_t r = 0; r < flt->n_rows; r++) {
+        const uint64_t* src = flt->rows + (size_t)r * Wc;
+        uint64_t* dst = flt_rows.data() + (size_t)r * s->W;
+        for (int k = 0; k < s->C; k++) {
+          const uint32_t c = s->perm[k];
+          dst[k >> 6] |= ((src[c >> 6] >> (c & 63)) & 1) << (k & 63);
+        }
+      }
+    }
+  }
   auto* bt = new kp_batch();
   std::unique_ptr<kp_batch> guard(bt);
   bt->snap = s;
   bt->B = (int)n;
   bt->hdr.resize(n);
+  bt->flt_plugins = flt_plugins;
+  bt->l_flt = std::move(flt_list);
   const auto tp0 = std::chrono::steady_clock::now();
   if (s->opts.multiple_pod_templates_scheduling)
     for (uint64_t i = 0; i < n; i++)
@@ -3460,6 +3517,10 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     a.add(&bt->d_est_cls, bt->l_est_cls.size());
     a.add(&bt->d_est_rows, est_rows.size());
   }
+  if (!bt->l_flt.empty()) {
+    a.add(&bt->d_flt_list, bt->l_flt.size());
+    a.add(&bt->d_flt_rows, flt_rows.size());
+  }
   const auto tp1 = std::chrono::steady_clock::now();
   HIPCHK(a.alloc());
   bt->h_kargs = (KArgs*)pinned_get(sizeof(KArgs) * kArgSlots, &bt->h_kargs_bytes);
@@ -3500,6 +3561,13 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     if (getenv("KP_PACK_TIMING"))
       fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
               bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + est_rows.size()));
+  }
+  if (!bt->l_flt.empty()) {
+    HIPCHK(up(bt->d_flt_list, bt->l_flt.data(), sizeof(FltPair) * bt->l_flt.size()));
+    HIPCHK(up(bt->d_flt_rows, flt_rows.data(), 8 * flt_rows.size()));
+    if (getenv("KP_PACK_TIMING"))
+      fprintf(stderr, "kp_batch_create_filters: %zu bindings with a row, %zu bytes uploaded for them\n",
+              bt->l_flt.size(), sizeof(FltPair) * bt->l_flt.size() + 8 * flt_rows.size());
   }
   HIPCHK(up(bt->d_all, bt->l_all.data(), 4 * bt->l_all.size()));
   bt->l_all_cls.resize(bt->l_all.size());
@@ -3674,12 +3742,20 @@ static const char* est_class_name(int fast) {
   return "k_est_class";
 }
 
-// The batch path computes the in-tree plugin set only (kp_options.n_out_of_tree_plugins).
-static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s) {
-  if (s->opts.n_out_of_tree_plugins == 0) return KP_OK;
+// The batch path computes the in-tree plugin set (kp_options.n_out_of_tree_plugins) and takes
+// the verdicts of out-of-tree filter plugins as rows (kp_batch_create_filters): a call runs
+// when the answers fold in exactly the plugins the registry holds (answered: the batch's
+// kp_filter_answers.n_plugins, 0 without answers and for the entry points that take none).
+static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s, uint32_t answered = 0) {
+  if (s->opts.n_out_of_tree_plugins == answered) return KP_OK;
   e->err = "the scheduler registry holds " + std::to_string(s->opts.n_out_of_tree_plugins) +
-           " filter/score plugin(s) outside the in-tree set: the batch path would ignore them "
-           "(schedule through the framework with the per-pair entry points)";
+           " filter/score plugin(s) outside the in-tree set";
+  if (answered)
+    e->err += " and the batch's filter answers fold in " + std::to_string(answered) +
+              " (kp_filter_answers.n_plugins must equal kp_options.n_out_of_tree_plugins)";
+  else
+    e->err += ": the batch path would ignore them (hand in filter-only plugins' verdicts with "
+              "kp_batch_create_filters, or schedule through the framework with the per-pair entry points)";
   return KP_ENOTSUP;
 }
 
@@ -3693,7 +3769,7 @@ static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s) {
 // kp_results_packed.
 static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
   if (!e || !bt) return KP_EINVAL;
-  if (int rc = refuse_out_of_tree(e, bt->snap)) return rc;
+  if (int rc = refuse_out_of_tree(e, bt->snap, bt->flt_plugins)) return rc;
   (void)dev::set_device(e->device);
   kp_snapshot* s = bt->snap;
   const int B = bt->B;
@@ -3810,6 +3886,11 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
                            bt->cls_rows));
     HIPCHK(dev::event_record(e->ev[5], sp));  // every class row is written (k_class_order's input)
     KPROF(sp, "k_filter", B, -1, dev::filter(sp, s->view, bt->view, bt->fmask));
+    // the out-of-tree filter verdicts ANDed into their bindings' rows, ahead of every reader
+    // of the feasibility rows (the feasible-only class rows next, then all behind ev[4])
+    if (!bt->l_flt.empty())
+      KPROF(sp, "k_filter_extra", bt->l_flt.size(), -1,
+            dev::filter_extra(sp, s->view, bt->d_flt_list, (int)bt->l_flt.size(), bt->d_flt_rows, bt->fmask, nullptr));
     if (single)  // the singleton classes' feasible entries, from the feasibility rows
       KPROF(sp, est_class_feasible_name(fast), bt->l_cls_single.size(), -1,
             dev::est_class(sp, s->view, bt->view, bt->d_crep, (int)bt->l_cls_single.size(), bt->cls_rows, fast,
@@ -3818,6 +3899,12 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
     KPROF(sp, pair_name(fast), B, -1,
           dev::pair(sp, s->view, bt->view, nullptr, 0, B, bt->fmask, bt->est, nullptr, 0, md_cap, smem_pair(s, md_cap),
                     fast));
+    // pair-row mode: the same AND, and the estimate rows zeroed where the row rejects, as
+    // the pair kernel leaves the clusters it found infeasible itself (k_rows_from_class and
+    // k_est_extra below then keep them 0)
+    if (!bt->l_flt.empty())
+      KPROF(sp, "k_filter_extra", bt->l_flt.size(), -1,
+            dev::filter_extra(sp, s->view, bt->d_flt_list, (int)bt->l_flt.size(), bt->d_flt_rows, bt->fmask, bt->est));
     if (int rc = sets_rows()) return rc;
   }
   if (!bits && !bt->l_sets.empty())
@@ -4537,6 +4624,9 @@ static int filter_batch_impl(kp_engine* e, kp_batch* bt, uint64_t* out_mask) {
     int rc = run_pair(e, bt, nullptr, 0, 0, bt->B);
     if (rc) return rc;
   }
+  if (!bt->l_flt.empty())  // the merged mask: the out-of-tree verdicts ANDed in
+    HIPCHK(dev::filter_extra(e->stream, s->view, bt->d_flt_list, (int)bt->l_flt.size(), bt->d_flt_rows, bt->fmask,
+                             nullptr));
   std::vector<uint64_t> m((size_t)bt->B * s->W);
   HIPCHK(dev::d2h(m.data(), bt->fmask, 8 * m.size(), e->stream));
   HIPCHK(dev::sync(e->stream));
@@ -4569,7 +4659,14 @@ static int filter_reasons_impl(kp_engine* e, kp_batch* bt, uint32_t* out_reasons
   int rc = KP_OK;
   for (int b0 = 0; b0 < bt->B && rc == KP_OK; b0 += nb) {
     const int m = std::min(nb, bt->B - b0);
-    if (dev::reasons(e->stream, s->view, bt->view, b0, m, d) || dev::d2h(h.data(), d, 4 * (size_t)m * s->C, e->stream) ||
+    // the chunk's bindings that have a row of out-of-tree verdicts (l_flt is in binding
+    // order): KP_REASON_OUT_OF_TREE substituted in the device buffer before the copy-back
+    auto below = [](const FltPair& p, int b) { return p.b < b; };
+    const size_t f0 = std::lower_bound(bt->l_flt.begin(), bt->l_flt.end(), b0, below) - bt->l_flt.begin();
+    const size_t f1 = std::lower_bound(bt->l_flt.begin(), bt->l_flt.end(), b0 + m, below) - bt->l_flt.begin();
+    if (dev::reasons(e->stream, s->view, bt->view, b0, m, d) ||
+        dev::reasons_extra(e->stream, s->view, bt->d_flt_list + f0, (int)(f1 - f0), bt->d_flt_rows, b0, d) ||
+        dev::d2h(h.data(), d, 4 * (size_t)m * s->C, e->stream) ||
         dev::sync(e->stream)) {
       e->err = std::string("kp_filter_reasons: ") + dev::last_error();
       rc = KP_EDEVICE;

@@ -137,6 +137,35 @@ extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_filter(SnapVie
 #else
 ;
 #endif
+// The out-of-tree filter verdicts ANDed into the listed bindings' feasibility rows (and, in
+// pair-row mode, their estimate rows zeroed where the row rejects): one wave64 per listed
+// binding, kFilterWaves per workgroup, the item index through a scalar register as k_filter.
+extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_filter_extra(int n, int C, int Cp, int W,
+                                                                             const FltPair* list,
+                                                                             const uint64_t* rows, uint64_t* fmask,
+                                                                             int32_t* est)
+#if KP_K(1)
+{
+  const int i = (int)(blockIdx.x * kFilterWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n) return;  // wave-uniform
+  body_filter_extra(GpuBlk{nullptr}, i, C, Cp, W, list, rows, fmask, est);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_reasons_extra(int n, int C, int W,
+                                                                              const FltPair* list,
+                                                                              const uint64_t* rows, int b0,
+                                                                              uint32_t* out)
+#if KP_K(1)
+{
+  const int i = (int)(blockIdx.x * kFilterWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n) return;  // wave-uniform
+  body_reasons_extra(GpuBlk{nullptr}, i, C, W, list, rows, b0, out);
+}
+#else
+;
+#endif
 // A launch over a device-appended list (a.n_dev) runs a grid-stride loop; otherwise
 // one workgroup per list entry (one iteration).
 // A workgroup without an entry returns before anything else: otherwise the body's
@@ -684,6 +713,22 @@ int filter(stream_t st, const SnapView& s, const BatchView& bv, uint64_t* fmask)
 static int spread_grid(const KArgs& a, const SelectExtra& x) {
   const int g = a.n_dev ? std::min(a.n, 256 * 4) : a.n;
   return a.n_dev && x.list_grid > 0 ? std::min(g, x.list_grid) : g;
+}
+
+int filter_extra(stream_t st, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, uint64_t* fmask,
+                 int32_t* est) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_filter_extra, dim3((n + kFilterWaves - 1) / kFilterWaves), dim3(64 * kFilterWaves), 0,
+                     (hipStream_t)st, n, s.C, s.Cp, s.W, list, rows, fmask, est);
+  return chk(hipGetLastError());
+}
+
+int reasons_extra(stream_t st, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, int b0,
+                  uint32_t* out) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_reasons_extra, dim3((n + kFilterWaves - 1) / kFilterWaves), dim3(64 * kFilterWaves), 0,
+                     (hipStream_t)st, n, s.C, s.W, list, rows, b0, out);
+  return chk(hipGetLastError());
 }
 
 int select(stream_t st, int which, const KArgs& a, size_t smem, int cap, const SelectExtra& x) {

@@ -66,6 +66,17 @@ int est_class(stream_t st, const SnapView& s, const BatchView& bv, const int32_t
 // Feasibility rows fmask[b][W] of every binding by bitset algebra (body_filter;
 // requires s.n_bits > 0).
 int filter(stream_t st, const SnapView& s, const BatchView& bv, uint64_t* fmask);
+// kp_batch_create_filters: the out-of-tree filter plugins' verdicts ANDed into the feasibility
+// rows of the n listed bindings (body_filter_extra): fmask[list[i].b] &= rows[list[i].r],
+// rows [..][W] words by cluster rank. est (pair-row mode, else null): those bindings' estimate
+// rows [..][Cp], zeroed where the row rejects.
+int filter_extra(stream_t st, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, uint64_t* fmask,
+                 int32_t* est);
+// kp_filter_reasons on such a batch: KP_REASON_OUT_OF_TREE into the reasons rows of the n
+// listed bindings (all within the chunk that starts at binding b0) where the in-tree set
+// fits and the row rejects (body_reasons_extra).
+int reasons_extra(stream_t st, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, int b0,
+                  uint32_t* out);
 int select(stream_t st, int which, const KArgs& a, size_t smem, int cap, const SelectExtra& x);
 // Region stage B of the wide-listed bindings that k_region_b marked (body_region_wide):
 // `grid` persistent workgroups, each with a slot of slot_bytes in scratch, over the rows

@@ -350,6 +350,45 @@ KP_UNROLL
   }
 }
 
+// The out-of-tree filter plugins' verdicts ANDed into the feasibility rows: item i is
+// binding list[i].b and its row list[i].r of `rows` ([..][W] words by cluster rank, zero
+// in the padding), by the calling wave (lane l takes words l, l + 64, ...: 8 bytes per
+// lane, coalesced; on the host build one "lane" walks them all). i is wave-uniform (the
+// kernel passes it through kp_uniform), so the pair and both row bases stay in scalar
+// registers. est (pair-row mode only, else null): the bindings' own estimate rows
+// ([..][Cp]), which the pair kernel zeroes on the clusters it found infeasible itself; the
+// clusters the row rejects are zeroed here in the same way, so a reader of such a row sees
+// what it would had the pair kernel known the verdict.
+template <class BLK>
+KP_FI void body_filter_extra(const BLK& B, int i, int C, int Cp, int W, const FltPair* list, const uint64_t* rows,
+                             uint64_t* fmask, int32_t* est) {
+  const FltPair p = kp_ldu(list + i);
+  const uint64_t* x = rows + (size_t)p.r * W;
+  uint64_t* row = fmask + (size_t)p.b * W;
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  for (int w = lane; w < W; w += ww) row[w] &= x[w];
+  if (est) {
+    int32_t* er = est + (size_t)p.b * Cp;
+    for (int c = lane; c < C; c += ww)
+      if (!((x[c >> 6] >> (c & 63)) & 1)) er[c] = 0;
+  }
+}
+
+// kp_filter_reasons on such a batch: item i's reasons row out[(list[i].b - b0) * C + rank]
+// (body_reasons wrote it) gets KP_REASON_OUT_OF_TREE (8, argument 0) where the in-tree set
+// fits (KP_REASON_FIT, a zero word) and the row rejects; every other word (an in-tree
+// reason, 255 for a deleting cluster) stays. One wave per item as above.
+template <class BLK>
+KP_FI void body_reasons_extra(const BLK& B, int i, int C, int W, const FltPair* list, const uint64_t* rows, int b0,
+                              uint32_t* out) {
+  const FltPair p = kp_ldu(list + i);
+  const uint64_t* x = rows + (size_t)p.r * W;
+  uint32_t* o = out + (size_t)(p.b - b0) * C;
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  for (int c = lane; c < C; c += ww)
+    if ((o[c] & 0xffu) == 0u && !((x[c >> 6] >> (c & 63)) & 1)) o[c] = 8u;
+}
+
 // Pair stage for binding list[b0 + blk] (b0 + blk without a list): each wave evaluates 64 consecutive clusters
 // (coalesced SoA columns), stores their feasibility as one u64 word and
 // calAvailableReplicas per cluster. est_mode 1: raw GeneralEstimator answers for

@@ -66,6 +66,12 @@ struct SelectExtra {
   // by-value kernel argument would be copied to scratch by every wave (~34 KB per wave)
   const KArgs* dargs = nullptr;
 };
+// A binding of kp_batch_create_filters that has a row of the out-of-tree filter plugins'
+// verdicts: (binding index, row id), the list sorted by binding index.
+struct FltPair {
+  int32_t b, r;
+};
+
 // device KArgs slots per batch (one per such launch in a schedule call)
 constexpr int kArgSlots = 16;
 

@@ -33,7 +33,7 @@ _LIBS = {}
 EXPORTS = (
     "kp_abi_version", "kp_engine_create", "kp_engine_destroy", "kp_last_error", "kp_snapshot_create",
     "kp_snapshot_destroy", "kp_snapshot_export", "kp_snapshot_import", "kp_snapshot_update", "kp_batch_create",
-    "kp_batch_destroy", "kp_batch_create_keyed", "kp_batch_create_estimates", "kp_batch_digest", "kp_pack_cache_create", "kp_pack_cache_destroy",
+    "kp_batch_destroy", "kp_batch_create_keyed", "kp_batch_create_estimates", "kp_batch_create_filters", "kp_batch_digest", "kp_pack_cache_create", "kp_pack_cache_destroy",
     "kp_pack_cache_get_stats",
     "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
     "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
@@ -80,6 +80,9 @@ def load_library(path: str = LIB_PATH):
                                         vp, C.POINTER(vp)]
     L.kp_batch_create_estimates.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.POINTER(api.kp_binding_key),
                                             C.c_uint64, vp, C.POINTER(api.kp_estimates), C.POINTER(vp)]
+    L.kp_batch_create_filters.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.POINTER(api.kp_binding_key),
+                                          C.c_uint64, vp, C.POINTER(api.kp_estimates),
+                                          C.POINTER(api.kp_filter_answers), C.POINTER(vp)]
     L.kp_schedule_batch.argtypes = [vp, vp, C.POINTER(api.kp_results)]
     L.kp_schedule_batch_submit.argtypes = [vp, vp]
     L.kp_schedule_batch_collect.argtypes = [vp, vp, C.POINTER(api.kp_results)]
@@ -345,10 +348,14 @@ class Batch:
     kp_batch_create_keyed: bindings whose record the cache holds skip packing. With
     `estimates` = (rows, row_of) it is created through kp_batch_create_estimates: rows is an
     int32 array [R, C] of the other estimators' merged answers (caller cluster order, -1 =
-    no answer), row_of each binding's row (-1 for none)."""
+    no answer), row_of each binding's row (-1 for none). With `filters` = (rows, row_of,
+    n_plugins) it is created through kp_batch_create_filters (together with `estimates`, if
+    given): rows is a bool array [R, C] of the out-of-tree filter plugins' ANDed verdicts
+    (caller cluster order, True = passed), row_of each binding's row (-1: no plugin
+    objected), n_plugins the number of registered out-of-tree plugins they fold in."""
 
     def __init__(self, snap: Snapshot, bindings: Sequence[dict] = (), structs=None, cache: "PackCache" = None,
-                 keys=None, generations: Sequence[int] = None, estimates=None):
+                 keys=None, generations: Sequence[int] = None, estimates=None, filters=None):
         self.snap = snap
         eng = snap.engine
         if structs is None:
@@ -361,11 +368,23 @@ class Batch:
         h = C.c_void_p()
         if cache is not None and keys is None:  # (uid from each binding, metadata.generation given)
             keys = api.binding_keys(ba, n, generations if generations is not None else [0] * n)
+        est = None
         if estimates is not None:
             rows, row_of = estimates
             if len(row_of) != n:
                 raise ValueError(f"estimates: row_of has {len(row_of)} entries for {n} bindings")
             est, self._est = api.estimates(rows, row_of)
+        if filters is not None:
+            rows, row_of, n_plugins = filters
+            if len(row_of) != n:
+                raise ValueError(f"filters: row_of has {len(row_of)} entries for {n} bindings")
+            flt, self._flt = api.filter_answers(rows, row_of, n_plugins)
+            self._keys = keys if cache is not None else None
+            eng._check(eng.L.kp_batch_create_filters(eng.h, snap.h, ba, self._keys, n,
+                                                     cache.h if cache is not None else None,
+                                                     C.byref(est) if est is not None else None, C.byref(flt),
+                                                     C.byref(h)), "kp_batch_create_filters")
+        elif estimates is not None:
             self._keys = keys if cache is not None else None
             eng._check(eng.L.kp_batch_create_estimates(eng.h, snap.h, ba, self._keys, n,
                                                        cache.h if cache is not None else None, C.byref(est),
@@ -610,9 +629,10 @@ class GenericScheduler:
             out.append(sr)
         return out
 
-    def filter(self, bindings: Sequence[dict]) -> List[List[str]]:
-        """Feasible cluster names per binding (findClustersThatFit)."""
-        b = Batch(self.snapshot, bindings)
+    def filter(self, bindings: Sequence[dict], filters=None) -> List[List[str]]:
+        """Feasible cluster names per binding (findClustersThatFit); filters: out-of-tree
+        filter verdicts (Batch's `filters=`), ANDed in."""
+        b = Batch(self.snapshot, bindings, filters=filters)
         eng = self.snapshot.engine
         C_ = len(self.snapshot.names)
         W = (C_ + 63) // 64
@@ -624,9 +644,11 @@ class GenericScheduler:
         b.close()
         return out
 
-    def filter_reasons(self, bindings: Sequence[dict]) -> List[List[int]]:
-        """kp_filter_reasons: the KP_REASON_* word of every (binding, cluster) pair."""
-        b = Batch(self.snapshot, bindings)
+    def filter_reasons(self, bindings: Sequence[dict], filters=None) -> List[List[int]]:
+        """kp_filter_reasons: the KP_REASON_* word of every (binding, cluster) pair; filters:
+        out-of-tree filter verdicts (Batch's `filters=`), reported as REASON_OUT_OF_TREE where
+        the in-tree set fits."""
+        b = Batch(self.snapshot, bindings, filters=filters)
         eng = self.snapshot.engine
         C_ = len(self.snapshot.names)
         r = (C.c_uint32 * max(1, b.n * C_))()
@@ -635,11 +657,18 @@ class GenericScheduler:
         b.close()
         return out
 
-    def fit_error(self, binding: dict, clusters: Sequence[dict]) -> str:
+    def fit_error(self, binding: dict, clusters: Sequence[dict], filters=None, out_of_tree=None) -> str:
         """FitError{NumAllClusters, Diagnosis}.Error() for one binding (generic_scheduler.go:84-89);
-        `clusters` are the snapshot's cluster dicts in its caller order."""
-        codes = self.filter_reasons([binding])[0]
-        reasons = {cl["name"]: api.reason_text(code, cl) for cl, code in zip(clusters, codes)
+        `clusters` are the snapshot's cluster dicts in its caller order. filters: the binding's
+        out-of-tree filter verdicts (Batch's `filters=`); out_of_tree: the text of
+        KP_REASON_OUT_OF_TREE, one string or {cluster name: text} (the rejecting plugin's own
+        reason: the engine sees the verdict only)."""
+        codes = self.filter_reasons([binding], filters=filters)[0]
+
+        def text(code, cl):
+            oot = out_of_tree.get(cl["name"]) if isinstance(out_of_tree, dict) else out_of_tree
+            return api.reason_text(code, cl, oot)
+        reasons = {cl["name"]: text(code, cl) for cl, code in zip(clusters, codes)
                    if code not in (api.REASON_FIT, api.REASON_DELETING)}
         return api.fit_error_message(len(clusters), reasons)
 

@@ -15,6 +15,11 @@ INTEGRATION.md implements them (the Python mirror the tests drive):
                                   kp_max_available_replicas (clusters in request order),
                                   MaxAvailableComponentSets through
                                   kp_max_available_component_sets
+  filter_only / FilterAnswers     the registry's out-of-tree plugins that implement
+                                  FilterPlugin alone, run once per distinct binding class and
+                                  folded into the rows of kp_filter_answers
+                                  (kp_batch_create_filters), so the batch path schedules
+                                  with them registered
   enabled_plugins_mask            `--plugins` (options.go:163) filtered over the in-tree
                                   registry (plugins/registry.go:33-50) as kp_options'
                                   enabled_plugins bitmask
@@ -162,8 +167,10 @@ class BatchView:
     pass over the one binding) never runs them. `clusters` are the snapshot's
     cluster dicts in caller order (for taint reasons)."""
 
-    def __init__(self, snap: Snapshot, batch: Batch, clusters: Optional[Sequence[dict]] = None):
+    def __init__(self, snap: Snapshot, batch: Batch, clusters: Optional[Sequence[dict]] = None,
+                 answers: Optional["FilterAnswers"] = None):
         self.snap, self.batch, self.clusters = snap, batch, clusters
+        self.answers = answers  # the batch's out-of-tree filter verdicts (KP_REASON_OUT_OF_TREE's texts)
         self.C = len(snap.names)
         self.index = {n: i for i, n in enumerate(snap.names)}
         self._reasons = self._scores = None
@@ -223,6 +230,8 @@ class KpFilter:
         code = w & 0xFF
         if code in (api.REASON_FIT, api.REASON_DELETING):
             return None
+        if code == api.REASON_OUT_OF_TREE:  # the rejecting plugin's own reasons
+            return Result(UNSCHEDULABLE, *(self.view.answers.reason(slot, cluster) if self.view.answers else []))
         cl = self.view.clusters[self.view.index[cluster]] if self.view.clusters is not None else {"taints": []}
         return Result(UNSCHEDULABLE, api.reason_text(w, cl))
 
@@ -290,6 +299,66 @@ def out_of_tree_plugins(registry_names: Sequence[str], shim_name: str = "KpPlace
     return sum(1 for n in registry_names if n not in IN_TREE and n != shim_name)
 
 
+def filter_only(plugins: Sequence[object]) -> bool:
+    """Whether every plugin implements FilterPlugin alone (no Score): only those plugins'
+    verdicts can be handed to the batch path (NormalizeScore runs over the feasible set)."""
+    return all(hasattr(p, "filter") and not hasattr(p, "score") for p in plugins)
+
+
+def spec_class_key(spec: dict) -> str:
+    """The default binding class of an out-of-tree filter: the spec's whole content (two
+    specs with equal content get equal verdicts from a plugin that reads the spec alone)."""
+    return json.dumps(spec, sort_keys=True, separators=(",", ":"), default=str)
+
+
+class FilterAnswers:
+    """The out-of-tree filter plugins' verdicts for one batch, as kp_filter_answers takes
+    them: the plugins run once per distinct binding class (class_key(spec)) and cluster, in
+    registry order with RunFilterPlugins' short circuit (runtime/framework.go:93-105);
+    `rows` is the bool array [R, C] of the classes some plugin objected to (caller cluster
+    order, True = every plugin returned Success), `row_of` each spec's row (-1: no plugin
+    objected), `reasons[row][cluster name]` the first rejecting plugin's reasons (the text
+    of KP_REASON_OUT_OF_TREE). plugin.filter((spec, cluster dict)) returns a Result or None."""
+
+    def __init__(self, plugins: Sequence[object], specs: Sequence[dict], clusters: Sequence[dict],
+                 class_key: Callable[[dict], str] = spec_class_key):
+        import numpy as np
+        if not filter_only(plugins):
+            bad = [p.name() for p in plugins if hasattr(p, "score") or not hasattr(p, "filter")]
+            raise ValueError(f"plugins {bad} are not filter-only: the batch path cannot take their answers")
+        self.n_plugins = len(plugins)
+        self.plugin_calls = 0
+        rows, self.reasons, self.row_of, by_class = [], [], [], {}
+        for sp in specs:
+            key = class_key(sp)
+            if key not in by_class:
+                ok, why = np.ones(len(clusters), dtype=bool), {}
+                for c, cl in enumerate(clusters):
+                    for p in plugins:
+                        self.plugin_calls += 1
+                        r = p.filter((sp, cl))
+                        if not is_success(r):
+                            ok[c] = False
+                            why[cl["name"]] = list(r.reasons)
+                            break
+                if ok.all():
+                    by_class[key] = -1
+                else:
+                    by_class[key] = len(rows)
+                    rows.append(ok)
+                    self.reasons.append(why)
+            self.row_of.append(by_class[key])
+        self.rows = np.array(rows, dtype=bool).reshape(len(rows), len(clusters))
+
+    def batch_arg(self):
+        """The `filters=` argument of engine.Batch."""
+        return self.rows, self.row_of, self.n_plugins
+
+    def reason(self, slot: int, cluster: str) -> List[str]:
+        r = self.row_of[slot]
+        return self.reasons[r].get(cluster, []) if r >= 0 else []
+
+
 def requirements_key(requirements: Optional[dict]) -> str:
     """The estimator cache key of a ReplicaRequirements: its content, canonically
     ordered (two requests with equal content share one device answer)."""
@@ -312,11 +381,15 @@ class Shim:
     * update(clusters) applies cluster events and destroys every view (their device
       arrays describe the old snapshot).
     The batch path refuses a registry with out-of-tree filter/score plugins
-    (kp_options.n_out_of_tree_plugins, KP_ENOTSUP); the per-pair answers stay available.
+    (kp_options.n_out_of_tree_plugins, KP_ENOTSUP) unless all of them are filter-only and
+    given as `filter_plugins` (instances, registry order): schedule_batch then runs them once
+    per distinct binding class and hands their verdicts in (kp_batch_create_filters). The
+    per-pair answers stay available either way.
     """
 
     def __init__(self, engine, clusters: Sequence[dict], opts: Optional[api.kp_options] = None,
-                 registry_names: Sequence[str] = ()):
+                 registry_names: Sequence[str] = (), filter_plugins: Sequence[object] = (),
+                 class_key: Callable[[dict], str] = spec_class_key):
         # a copy: the caller's kp_options stays as it was (reusing it for another
         # snapshot must not carry this shim's out-of-tree count)
         opts = api.kp_options.from_buffer_copy(opts) if opts is not None else api.options()
@@ -331,14 +404,21 @@ class Shim:
         # packed records kept across cycles, keyed by (uid, metadata.generation): the Go
         # shim's kp_pack_cache (INTEGRATION.md ScheduleBatchKeyed)
         self.pack_cache = PackCache(engine)
+        self.filter_plugins, self.class_key = list(filter_plugins), class_key
+        if self.filter_plugins and not filter_only(self.filter_plugins):
+            raise ValueError("Shim: filter_plugins must implement FilterPlugin alone (no Score)")
 
     def _view(self, specs: Sequence[dict], generations: Optional[Sequence[int]] = None) -> BatchView:
+        answers = filters = None
+        if self.filter_plugins:
+            answers = FilterAnswers(self.filter_plugins, specs, self.clusters, self.class_key)
+            filters = answers.batch_arg()
         if generations is None:
-            b = Batch(self.snap, list(specs))
+            b = Batch(self.snap, list(specs), filters=filters)
         else:
-            b = Batch(self.snap, list(specs), cache=self.pack_cache, generations=generations)
+            b = Batch(self.snap, list(specs), cache=self.pack_cache, generations=generations, filters=filters)
         self.batches_created += 1
-        return BatchView(self.snap, b, self.clusters)
+        return BatchView(self.snap, b, self.clusters, answers)
 
     def _register(self, view: BatchView, specs: Sequence[dict]):
         for i, sp in enumerate(specs):

@@ -112,6 +112,43 @@ static int run_case(kp_engine* e, int config, uint64_t seed, uint32_t C, uint64_
       }
       if (be) kp_batch_destroy(be);
     }
+    // the same bindings through kp_batch_create_filters against a registry holding one
+    // out-of-tree filter plugin, with rows that reject nothing (all ones, stray bits above the
+    // cluster count in the last word), every third binding without a row: the rank-order
+    // upload, k_filter_extra, the merged mask and the reasons pass run, the placements stay
+    {
+      const uint64_t wc = (nc + 63) / 64;
+      std::vector<uint64_t> rows(2 * wc, ~0ull);
+      std::vector<int32_t> row_of(nb);
+      for (uint64_t i = 0; i < nb; i++) row_of[i] = (int32_t)(i % 3) - 1;
+      const kp_filter_answers flt{2, nc, rows.data(), row_of.data(), 1};
+      kp_options o1 = o;
+      o1.n_out_of_tree_plugins = 1;
+      kp_snapshot* s1 = nullptr;
+      kp_batch* bf = nullptr;
+      kp_results rf{};
+      std::vector<uint64_t> mask(nb * wc + 1);
+      std::vector<uint32_t> reasons(nb * nc + 1);
+      if (kp_snapshot_create(e, cl, nc, &o1, &s1) || kp_batch_create_filters(e, s1, bs, nullptr, nb, nullptr, nullptr, &flt, &bf) ||
+          kp_filter_batch(e, bf, mask.data()) || kp_filter_reasons(e, bf, reasons.data()) || kp_schedule_batch(e, bf, &rf)) {
+        fprintf(stderr, "config %d: filters: engine error: %s\n", config, kp_last_error(e));
+        bad++;
+      } else {
+        for (uint64_t i = 0; i < nb; i++) {
+          const bool same = rf.status[i] == want->status[i] && rf.err_code[i] == want->err_code[i] &&
+                            rf.err_arg[i] == want->err_arg[i] &&
+                            targets_of(rf.offsets, rf.cluster_idx, rf.replicas, i) ==
+                                targets_of(want->offsets, want->cluster_idx, want->replicas, i);
+          if (!same && bad++ < 3) fprintf(stderr, "config %d seed %llu binding %llu differs (filters)\n", config,
+                                          (unsigned long long)seed, (unsigned long long)i);
+        }
+        for (uint64_t k = 0; k < nb * nc; k++)
+          if ((reasons[k] & 0xff) == KP_REASON_OUT_OF_TREE && bad++ < 3)
+            fprintf(stderr, "config %d: an all-ones row rejected pair %llu\n", config, (unsigned long long)k);
+      }
+      if (bf) kp_batch_destroy(bf);
+      if (s1) kp_snapshot_destroy(s1);
+    }
     kpo_results_free(want);
     kpo_world_destroy(ow);
   }
