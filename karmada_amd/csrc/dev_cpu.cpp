@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kp_dev.h"
+#include "kp_env.h"
 #include "kp_sets.h"
 #include "kp_kernels.h"
 #include "kp_top.h"
@@ -22,8 +23,7 @@ namespace dev {
 
 namespace {
 int threads() {
-  const char* e = getenv("KP_CPUSIM_THREADS");
-  int n = e ? atoi(e) : 1;
+  const int n = (int)kp_env_int("KP_CPUSIM_THREADS", 1);
   return n < 1 ? 1 : n;
 }
 // GPU LDS is not zeroed at launch and keeps whatever the previous workgroup on
@@ -31,10 +31,7 @@ int threads() {
 // KP_CPUSIM_POISON=0 turns it off), so a read of LDS the kernel never wrote
 // gives garbage here as it would on the device, not a convenient zero.
 bool poison() {
-  static const bool on = [] {
-    const char* e = getenv("KP_CPUSIM_POISON");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = kp_env_int("KP_CPUSIM_POISON", 1) != 0;
   return on;
 }
 // Runs fn(blk, smem) for blk in [0, n) on the configured host threads.
@@ -68,8 +65,7 @@ struct Ev {
 
 // Emulated devices (the multi-device engine's tests): KP_CPUSIM_DEVICES, default 8.
 int device_count() {
-  const char* e = getenv("KP_CPUSIM_DEVICES");
-  const int n = e ? atoi(e) : 8;
+  const int n = (int)kp_env_int("KP_CPUSIM_DEVICES", 8);
   return n < 1 ? 1 : n;
 }
 int set_device(int) { return 0; }
@@ -206,16 +202,15 @@ int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const Sele
       // appended it, so which bindings follow each other in one workgroup's slot
       // varies from run to run. KP_CPUSIM_SLOW_SHUFFLE=<seed> permutes the list and
       // KP_CPUSIM_SLOW_GRID=<g> narrows the grid, to replay such orders here.
-      if (const char* sh = getenv("KP_CPUSIM_SLOW_SHUFFLE")) {
-        uint64_t r = (uint64_t)atoll(sh) * 0x9E3779B97F4A7C15ull + 1;
+      if (kp_env_flag("KP_CPUSIM_SLOW_SHUFFLE")) {
+        uint64_t r = (uint64_t)kp_env_int("KP_CPUSIM_SLOW_SHUFFLE", 0) * 0x9E3779B97F4A7C15ull + 1;
         const int ns = (int)std::min<uint32_t>(a.stats[0], (uint32_t)a.n);
         for (int i = ns - 1; i > 0; i--) {
           r ^= r << 13, r ^= r >> 7, r ^= r << 17;
           std::swap(a.slow_ids[i], a.slow_ids[(int)(r % (uint64_t)(i + 1))]);
         }
       }
-      int g = x.grid;
-      if (const char* sg = getenv("KP_CPUSIM_SLOW_GRID")) g = std::max(1, std::min(g, atoi(sg)));
+      const int g = std::max(1, std::min(x.grid, (int)kp_env_int("KP_CPUSIM_SLOW_GRID", x.grid)));
       grid(g, smem, [&](int blk, unsigned char* sm) {
         body_slow(CpuBlk{(int64_t*)sm}, blk, g, sm, a, x.scratch, x.slot_bytes, cap, x.lds_area, x.lds_sort);
       });
@@ -249,12 +244,6 @@ int class_order(stream_t, const SnapView& s, const int32_t* rows, int n_rows, ui
 
 int select_top(stream_t, const KArgs& a, const TopArgs& t, size_t slice, int) {
   grid(a.n_dev ? (int)*a.n_dev : a.n, slice, [&](int blk, unsigned char* sm) { body_select_top(CpuBlk{(int64_t*)sm}, blk, sm, a, t); });
-  return 0;
-}
-int select_top_wg(stream_t, const KArgs& a, const TopArgs& t, size_t smem) {
-  grid(a.n, smem, [&](int blk, unsigned char* sm) {
-    body_select_top_wg(CpuBlk{(int64_t*)sm}, CpuBlk{(int64_t*)top_wg_slice(sm)}, blk, sm, a, t);
-  });
   return 0;
 }
 
@@ -353,11 +342,10 @@ int offsets(stream_t, const int32_t* status, const uint32_t* count, int n, uint6
 }
 
 int compact(stream_t, const uint64_t* start, const uint32_t* count, const uint64_t* offsets, const uint32_t* in_idx,
-            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm, uint32_t* h_idx,
-            int32_t* h_rep, uint64_t h_cap) {
+            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm) {
   int64_t red[8];
   for (int b = 0; b < n; b++)
-    body_compact(CpuBlk{red}, b, start, count, offsets, in_idx, in_rep, out_idx, out_rep, n, perm, h_idx, h_rep, h_cap);
+    body_compact(CpuBlk{red}, b, start, count, offsets, in_idx, in_rep, out_idx, out_rep, n, perm);
   return 0;
 }
 int pack(stream_t, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx, const int32_t* in_rep,
@@ -370,10 +358,6 @@ int pack_wide(stream_t, const uint64_t* start, const uint64_t* offsets, const ui
               const int32_t* in_rep, int32_t* out, int n) {
   int64_t red[8];
   for (int b = 0; b < n; b++) body_pack_wide(CpuBlk{red}, b, start, offsets, wide_offsets, in_rep, out, n);
-  return 0;
-}
-int host_device_ptr(void* host, void** dev) {
-  *dev = host;
   return 0;
 }
 

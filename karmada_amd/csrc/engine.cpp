@@ -26,6 +26,7 @@
 
 #include "../../include/kp/kp_api.h"
 #include "k8s.h"
+#include "kp_env.h"
 #include "kp_layout.h"
 #include "kp_launch.h"
 #include "kp_paths.h"
@@ -309,21 +310,6 @@ struct kp_engine {
   int top_cap_mid = 0;
   bool top_split = true;    // the two slices' launches on two streams (KP_TOP_SPLIT=0: one)
   bool slow_order = true;   // k_slow orders candidates from the class orders (KP_SLOW_ORDER=0: sorts)
-  // with a region chain (whose host steps synchronise anyway) the fallback kernels over
-  // device-appended lists are launched only after their counts are read back, so none runs
-  // with an empty list (KP_GATE_FB=0: always launched, each workgroup reading the count;
-  // 2: only the SEL_ALL and cluster-spread fallbacks, at k_slow's existing count read,
-  // not the region fallbacks, whose reads add two host waits to the region chain)
-  int gate_fb = 1;
-  // KP_ZC=1: k_compact writes the result CSR into the page-locked buffers over the bus
-  // (no copy, no size read-back); measured slower with batches in flight (its workgroups
-  // hold CUs while their stores cross the bus: 51-53 vs 71-85 M/s), so off
-  bool zc = false;
-  // KP_SPEC_COPY=1: a batch scheduled again copies its previous CSR size ahead of the
-  // total's read-back (one host round trip per call); measured no better with batches in
-  // flight (59.7-81.5 vs 69.2-88.9 M/s, same box), so off
-  bool spec_copy = false;
-  bool top_wg = false;      // large-subset bindings on k_select_top_wg (KP_TOP_WG=1; measured slower)
   // per-kernel timing of kp_schedule_batch (kp_engine_set_profile): an event pair
   // around every launch on its own stream, folded by kernel name after the batch
   struct KProf {
@@ -372,11 +358,11 @@ struct kp_snapshot {
 // diagnostic builds: phase stamps and counters, kDbgSlots x kDbgSpread (kp_select.h)
 // The state schedule_submit leaves for schedule_finish (one submitted call per batch).
 struct SchedPend {
-  bool live = false, empty = false, zc = false, bits = false, top = false, spread_orders = false;
+  bool live = false, empty = false, bits = false, top = false, spread_orders = false;
   bool packed = false;  // the call returns kp_results_packed (kp_schedule_batch_submit_packed)
   int fast = 0;
   double t0 = 0, th0 = 0, th1 = 0;
-  uint64_t spec = 0, seq = 0;
+  uint64_t seq = 0;
   dev::event_t ev = nullptr;  // recorded after the call's last read-back (kept across calls)
 };
 
@@ -495,7 +481,6 @@ struct kp_batch {
   uint32_t* h_cidx = nullptr;
   int32_t* h_crep = nullptr;
   uint64_t h_res_cap = 0;
-  uint64_t last_tot = 0;  // the previous call's CSR size (the speculative copy)
   SchedPend pend;         // a submitted call (schedule_submit) awaiting schedule_finish
   size_t h_cidx_bytes = 0, h_crep_bytes = 0;  // their pooled block sizes
   // The packed result form (kp_results_packed), allocated on the batch's first packed call
@@ -2133,8 +2118,7 @@ int kp_engine_create(int device, kp_engine** out) {
   // fit the default queues with fewer streams each. 2: the result/region stream and the
   // SEL_ALL stream are one (the class orders and the large select_top slice keep their
   // own); 1: every launch of the call in one stream.
-  int n_streams = 3;
-  if (const char* v = getenv("KP_STREAMS")) n_streams = std::max(1, std::min(3, atoi(v)));
+  const int n_streams = (int)std::max(1ll, std::min(3ll, kp_env_int("KP_STREAMS", 3)));
   bool fail = dev::set_device(device) || dev::stream_create(&e->stream);
   if (!fail && n_streams >= 3) fail = dev::stream_create(&e->stream2) != 0;
   else e->stream2 = e->stream;
@@ -2149,18 +2133,14 @@ int kp_engine_create(int device, kp_engine** out) {
   }
   for (auto& ev : e->ev) (void)dev::event_create(&ev);
   e->max_lds = dev::max_lds_per_block(device);
-  if (const char* v = getenv("KP_TOP")) e->top_on = atoi(v) != 0;
-  if (const char* v = getenv("KP_TOP_SPLIT")) e->top_split = atoi(v) != 0;
-  if (const char* v = getenv("KP_SLOW_ORDER")) e->slow_order = atoi(v) != 0;
-  if (const char* v = getenv("KP_GATE_FB")) e->gate_fb = atoi(v);
-  if (const char* v = getenv("KP_ZC")) e->zc = atoi(v) != 0;
-  if (const char* v = getenv("KP_SPEC_COPY")) e->spec_copy = atoi(v) != 0;
-  if (const char* v = getenv("KP_TOP_WG")) e->top_wg = atoi(v) != 0;
-  if (const char* v = getenv("KP_TOP_CAP")) {  // (tests: one capacity for both slices)
-    e->top_cap = std::max(64, std::min(1024, atoi(v) & ~63));
+  e->top_on = kp_env_int("KP_TOP", 1) != 0;
+  e->top_split = kp_env_int("KP_TOP_SPLIT", 1) != 0;
+  e->slow_order = kp_env_int("KP_SLOW_ORDER", 1) != 0;
+  if (kp_env_flag("KP_TOP_CAP")) {  // (tests: one capacity for both slices)
+    e->top_cap = std::max(64, std::min(1024, (int)kp_env_int("KP_TOP_CAP", 0) & ~63));
     e->top_cap_small = std::min(e->top_cap_small, e->top_cap);
   }
-  if (const char* v = getenv("KP_TOP_CAP_MID")) e->top_cap_mid = std::max(0, std::min(1024, atoi(v) & ~63));
+  e->top_cap_mid = std::max(0, std::min(1024, (int)kp_env_int("KP_TOP_CAP_MID", 0) & ~63));
   unsigned hc = std::thread::hardware_concurrency();
   e->n_threads = (int)std::max(1u, std::min(16u, hc));
   *out = e;
@@ -2531,10 +2511,7 @@ KP_HD inline bool route_static_ok(const SnapView& v, const BindHdr& h, const int
 // Replicas + len(spec.Clusters) up to which a binding takes k_select_top's small slice
 // (KP_TOP_SMALL_NEED overrides kTopSmallNeed, for measurement).
 inline int64_t top_small_need() {
-  static const int64_t v = [] {
-    const char* e = getenv("KP_TOP_SMALL_NEED");
-    return e ? std::max<int64_t>(0, atoll(e)) : kTopSmallNeed;
-  }();
+  static const int64_t v = std::max<int64_t>(0, kp_env_int("KP_TOP_SMALL_NEED", kTopSmallNeed));
   return v;
 }
 inline uint8_t route_of(const SnapView& v, const BindHdr& h, const int64_t* lpool) {
@@ -2738,8 +2715,7 @@ static inline uint64_t cache_key(const kp_binding_key& k) {
 // class key after the record lookup, so a cached record keeps the request key alone.
 bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* bt, const kp_binding_key* keys = nullptr,
                    kp_pack_cache* cache = nullptr, const int32_t* row_of = nullptr) {
-  int T = host_cpus();
-  if (const char* v = getenv("KP_PACK_THREADS")) T = atoi(v);
+  int T = (int)kp_env_int("KP_PACK_THREADS", host_cpus());
   T = std::max(1, std::min(T, n / 4096));
   // Chunks of kPackChunk bindings taken from a shared counter (a thread that meets heavy
   // bindings takes fewer chunks); each chunk packs into its own pools, concatenated in
@@ -3072,7 +3048,7 @@ bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* 
       left--;
     }
   }
-  if (getenv("KP_PACK_TIMING")) {
+  if (kp_env_flag("KP_PACK_TIMING")) {
     auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     fprintf(stderr, "pack_parallel: %d threads, %d chunks, pack %.1f ms, merge+classes %.1f ms; per thread", T, K,
             ms(tq0, tq1), ms(tq1, std::chrono::steady_clock::now()));
@@ -3091,8 +3067,7 @@ bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* 
 
 // Bindings per estimator class below which a batch skips the class orders.
 static int64_t order_amort() {  // (read per batch: tests switch it)
-  const char* e = getenv("KP_ORDER_AMORT");
-  return e ? std::max<int64_t>(0, atoll(e)) : (int64_t)4;
+  return std::max<int64_t>(0, kp_env_int("KP_ORDER_AMORT", 4));
 }
 
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
@@ -3304,29 +3279,6 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     bt->n_all_dyn = n_dyn;
     bt->n_top_small = n_small;
     bt->n_static = n_stat_ok;
-    // KP_SPREAD_GROUP=1: the spread lists grouped by estimator class too (stable), as the
-    // SEL_ALL list is; measured no better (config 4 3.84 vs 3.74 ms), so binding order
-    static const bool spread_group = [] {
-      const char* v = getenv("KP_SPREAD_GROUP");
-      return v && atoi(v) != 0;
-    }();
-    if (spread_group)
-      for (std::vector<int32_t>* lst : {&bt->l_cluster, &bt->l_region}) {
-        if (lst->size() < 2) continue;
-        std::vector<int32_t> c2(ncls + 1, 0), o2(lst->size());
-        for (int32_t b : *lst) c2[(size_t)std::max(0, bt->bcls[b]) + 1]++;
-        for (size_t k = 1; k <= ncls; k++) c2[k] += c2[k - 1];
-        for (int32_t b : *lst) o2[(size_t)c2[(size_t)std::max(0, bt->bcls[b])]++] = b;
-        lst->swap(o2);
-      }
-    // KP_TOP_LPT=1: the large-subset part heaviest first (replicas desc) instead of by class
-    static const bool lpt = [] {
-      const char* v = getenv("KP_TOP_LPT");
-      return v && atoi(v) != 0;
-    }();
-    if (lpt)
-      std::stable_sort(bt->l_all.begin() + n_small, bt->l_all.begin() + n_dyn,
-                       [&](int32_t x, int32_t y) { return bt->hdr[x].replicas > bt->hdr[y].replicas; });
   }
   bt->l_slow = bt->l_all;
   bt->l_slow.insert(bt->l_slow.end(), bt->l_cluster.begin(), bt->l_cluster.end());
@@ -3346,8 +3298,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     // diagnostic, keeps them in the global slot), as k_slow's
     int P = 1;
     while (P < s->Cp) P <<= 1;
-    const char* g = getenv("KP_WIDE_LDS");
-    if (!(g && g[0] == '0') && region_wide_lds_bytes(s->Cp, s->view.n_regions, 8 * P) <= e->max_lds)
+    if (kp_env_int("KP_WIDE_LDS", 1) != 0 && region_wide_lds_bytes(s->Cp, s->view.n_regions, 8 * P) <= e->max_lds)
       bt->wide_sort = 8 * P;
   }
   if (batch_lds_check(e, s, bt)) return KP_ENOTSUP;
@@ -3386,8 +3337,8 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   bt->slow_grid = (int)std::max<size_t>(1, std::min<size_t>(256, bt->l_slow.size()));
   // diagnostics: KP_SLOW_GRID=<g> caps k_slow's grid, KP_SLOW_LDS=0 keeps its sort
   // keys and scale-down scratch in the global slot (no LDS sort, no wave sort.Sort)
-  if (const char* g = getenv("KP_SLOW_GRID")) bt->slow_grid = std::max(1, std::min(bt->slow_grid, atoi(g)));
-  if (const char* g = getenv("KP_SLOW_LDS"); g && g[0] == '0') bt->slow_sort = bt->slow_lds = 0;
+  bt->slow_grid = std::max(1, std::min(bt->slow_grid, (int)kp_env_int("KP_SLOW_GRID", bt->slow_grid)));
+  if (kp_env_int("KP_SLOW_LDS", 1) == 0) bt->slow_sort = bt->slow_lds = 0;
   if (!bt->l_region_wide.empty()) {
     // one slot per workgroup; the grid capped so the slots stay within 256 MB (a slot is
     // ~37 MB at Cp = 262144, ~0.8 MB at C = 5000)
@@ -3465,10 +3416,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   const bool with_orders = s->C <= 16384 && !bt->crep.empty() && orders_pay && kRedBytes + 8 * (size_t)P <= e->max_lds;
   // singleton classes: feasible entries only, when every reader gathers feasible candidates
   // (no class orders, which sort whole rows; no spread lists; no component-set classes)
-  static const bool est_single_on = [] {
-    const char* v = getenv("KP_EST_SINGLE");
-    return !v || atoi(v) != 0;
-  }();
+  static const bool est_single_on = kp_env_int("KP_EST_SINGLE", 1) != 0;
   if (est_single_on && !with_orders && bt->crep.size() > 1 && bt->l_cluster.empty() && bt->l_region.empty() &&
       bt->sets_cls.empty()) {
     std::vector<int32_t> cnt(bt->crep.size(), 0);
@@ -3499,8 +3447,8 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     for (uint64_t i = 0; i < n; i++)
       if (bt->hdr[i].flags & BF_SETS) bt->l_sets.push_back((int32_t)i);
     sets_off.assign((size_t)s->C + 1, 0);
-    int64_t runs_cap = kSetsRunsMax;  // (KP_SETS_RUNS_CAP lowers it: tests of the overflow report)
-    if (const char* v = getenv("KP_SETS_RUNS_CAP")) runs_cap = std::max<int64_t>(1, std::min<int64_t>(atoll(v), kSetsRunsMax));
+    // (KP_SETS_RUNS_CAP lowers it: tests of the overflow report)
+    const int64_t runs_cap = std::max<int64_t>(1, std::min<int64_t>(kp_env_int("KP_SETS_RUNS_CAP", kSetsRunsMax), kSetsRunsMax));
     for (int r = 0; r < s->C; r++) {
       int64_t nodes = 0;
       for (int g = s->mgrp_off[r]; g < s->mgrp_off[r + 1]; g++) nodes += s->mgrp_cnt[g];
@@ -3558,14 +3506,14 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     HIPCHK(up(bt->d_cls_est, bt->cls_est.data(), 4 * bt->cls_est.size()));
     HIPCHK(up(bt->d_est_cls, bt->l_est_cls.data(), 4 * bt->l_est_cls.size()));
     HIPCHK(up(bt->d_est_rows, est_rows.data(), 4 * est_rows.size()));
-    if (getenv("KP_PACK_TIMING"))
+    if (kp_env_flag("KP_PACK_TIMING"))
       fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
               bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + est_rows.size()));
   }
   if (!bt->l_flt.empty()) {
     HIPCHK(up(bt->d_flt_list, bt->l_flt.data(), sizeof(FltPair) * bt->l_flt.size()));
     HIPCHK(up(bt->d_flt_rows, flt_rows.data(), 8 * flt_rows.size()));
-    if (getenv("KP_PACK_TIMING"))
+    if (kp_env_flag("KP_PACK_TIMING"))
       fprintf(stderr, "kp_batch_create_filters: %zu bindings with a row, %zu bytes uploaded for them\n",
               bt->l_flt.size(), sizeof(FltPair) * bt->l_flt.size() + 8 * flt_rows.size());
   }
@@ -3580,7 +3528,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   HIPCHK(up(bt->d_cs, bt->l_cs.data(), 4 * bt->l_cs.size()));
   HIPCHK(dev::fill(bt->slow, 0, 4 * (size_t)B, e->stream));
   HIPCHK(dev::sync(e->stream));
-  if (getenv("KP_PACK_TIMING")) {
+  if (kp_env_flag("KP_PACK_TIMING")) {
     const auto tp3 = std::chrono::steady_clock::now();
     auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     fprintf(stderr, "kp_batch_create: pack %.1f ms, alloc %.1f ms, upload %.1f ms\n", ms(tp0, tp1), ms(tp1, tp2),
@@ -3767,100 +3715,109 @@ static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s, uint32_t answe
 // packed: the results are gathered in the packed form (k_pack, the escape counts' scan,
 // k_pack_wide) instead of the CSR (k_compact), for schedule_finish to return as
 // kp_results_packed.
-static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
-  if (!e || !bt) return KP_EINVAL;
-  if (int rc = refuse_out_of_tree(e, bt->snap, bt->flt_plugins)) return rc;
-  (void)dev::set_device(e->device);
-  kp_snapshot* s = bt->snap;
-  const int B = bt->B;
-  if (packed && s->C > 65536) {  // (kp_batch_create's LDS bound refuses such snapshots long before)
-    e->err = "kp_schedule_batch_packed: a packed cluster index holds 16 bits (more than 65536 clusters)";
-    return KP_ENOTSUP;
-  }
-  if (packed && ensure_packed(e, bt)) return KP_EDEVICE;
-  double t0 = now_ms();
-  kp_stage_times tm{};
-  dev::stream_t st = e->stream;
-  SchedPend& pd = bt->pend;
-  {
-    const dev::event_t ev = pd.ev;  // (the event is kept across calls)
-    pd = SchedPend{};
-    pd.ev = ev;
-  }
-  pd.packed = packed;
-  pd.t0 = t0;
-  pd.seq = ++e->submit_seq;
-  if (B == 0) {
-    pd.empty = true;
-    pd.live = true;
-    return KP_OK;
-  }
-  if (!bt->l_region.empty() && s->view.n_regions != bt->n_regions) {
-    e->err = "kp_schedule_batch: the snapshot's region set changed since the batch was packed (re-create it)";
-    return KP_ESTATE;
-  }
-  if (batch_lds_check(e, s, bt)) return KP_ENOTSUP;
-  e->pk.clear();
-  HIPCHK(dev::h2d(bt->counter, &bt->out_cap, sizeof(unsigned long long), st));  // the shared area's start
-  HIPCHK(dev::fill(bt->stats, 0, sizeof(bt->h_stats), st));
-  if (!bt->sets_cls.empty()) HIPCHK(dev::fill(bt->d_sets_ovf, 0, 4 * bt->sets_cls.size(), st));
-  KArgs ka;
-  ka.s = s->view;
-  ka.bv = bt->view;
-  ka.fmask = bt->fmask;
-  ka.est = bt->est;
-  ka.sink.out_idx = bt->out_idx;
-  ka.sink.out_rep = bt->out_rep;
-  ka.sink.counter = bt->counter;
-  ka.sink.status = bt->status;
-  ka.sink.err = bt->errc;
-  ka.sink.arg = bt->arg;
-  ka.sink.start = bt->start;
-  ka.sink.count = bt->count;
-  ka.sink.cap_end = std::max<uint64_t>(1, 2 * bt->out_cap);
-  ka.slow = bt->slow;
-  ka.stats = bt->stats;
-  ka.slow_ids = bt->d_slowlist;
-  ka.dbg = bt->dbg;
-#if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
-  HIPCHK(dev::fill(bt->dbg, 0, kDbgSlots * kDbgSpread * 8, st));
-#endif
-  dev::stream_t sp = e->stream2;
-  HIPCHK(dev::event_record(e->ev[0], st));
-  HIPCHK(dev::stream_wait(sp, e->ev[0]));  // the fills above precede every kernel
-  const int fast = getenv("KP_PAIR_GENERIC") || !bt->fast_ok ? EST_GENERIC : s->est_kind;
-  const int md_cap = md_cap_of(s);
+//
+// schedule_submit queues the call in six stages (submit_rows ... submit_results, in that
+// order) over the engine's three streams; SubmitCtx is what the stages share.
+struct SubmitCtx {
+  kp_engine* e;
+  kp_batch* bt;
+  kp_snapshot* s;
+  bool packed;
+  KArgs ka;       // the batch's launch arguments: a launch copies them and sets its list
+  SelectExtra sx;
+  int kslot = 0;  // device argument slots taken so far (with_args)
+  int fast;       // the EST_* pair-kernel instance
   // Feasibility and calAvailableReplicas: by default (fast estimator instance and
   // the snapshot's bitset rows built) the filter runs as bitset algebra (k_filter)
   // and the estimator once per estimator class (k_est_class), kp_filter.h; else
   // (or KP_PAIR_ROWS=1) the pair kernel writes every binding's rows.
-  const bool bits = fast != EST_GENERIC && s->view.n_bits > 0 && !getenv("KP_PAIR_ROWS");
-  if (!bits && ensure_rows(e, bt)) return KP_EDEVICE;
-  ka.est = bits ? bt->cls_rows : bt->est;
-  ka.bcls = bits ? bt->d_bcls : nullptr;
-  SelectExtra sx;
-  sx.rout = bt->rout;
-  sx.rstat = bt->rstat;
-  sx.rsel = bt->rsel;
-  sx.rnsel = bt->rnsel;
-  sx.scratch = bt->slow_scratch;
-  sx.slot_bytes = bt->slow_slot;
-  sx.grid = bt->slow_grid;
-  sx.lds_area = bt->slow_lds;
-  sx.lds_sort = bt->slow_sort;
-  const int cap = kSmallMax + kTgtSmallMax + 16;
+  bool bits;
+  int top_cap, top_cap_small;  // k_select_top's subset capacities for this snapshot
+  bool top;                    // SEL_ALL DynamicWeight / Aggregated over the deciding candidates (kp_top.h)
+  // class orders: k_select_top's walk, and the spread selections over them
+  // (k_spread_order, k_region_a_order), each where its LDS slices fit the device
+  bool spread_orders, orders;
+  // Fallback launches over device-appended lists, with a region chain: their counts are
+  // read back where the host synchronises anyway (the region chain, k_slow's count), so a
+  // list left empty launches nothing; the SEL_ALL and cluster-spread fallbacks move to
+  // stream3 after that read, before k_slow (f_def / cl_def: their arguments until then).
+  // A batch without a region chain queues every fallback, each workgroup reading the count.
+  bool gate;
+  bool defer_all = false, defer_all_stream = false, defer_cl = false;
+  KArgs f_def{}, cl_def{};
+  double th0 = 0, th1 = 0;  // the region chain's host step
+  static constexpr int cap = kSmallMax + kTgtSmallMax + 16;
+
+  SubmitCtx(kp_engine* e_, kp_batch* bt_, bool packed_) : e(e_), bt(bt_), s(bt_->snap), packed(packed_) {
+    fast = kp_env_flag("KP_PAIR_GENERIC") || !bt->fast_ok ? EST_GENERIC : s->est_kind;
+    bits = fast != EST_GENERIC && s->view.n_bits > 0 && !kp_env_flag("KP_PAIR_ROWS");
+    ka.s = s->view;
+    ka.bv = bt->view;
+    ka.fmask = bt->fmask;
+    ka.est = bits ? bt->cls_rows : bt->est;  // (rows mode: set again once ensure_rows has allocated them)
+    ka.bcls = bits ? bt->d_bcls : nullptr;
+    ka.sink.out_idx = bt->out_idx;
+    ka.sink.out_rep = bt->out_rep;
+    ka.sink.counter = bt->counter;
+    ka.sink.status = bt->status;
+    ka.sink.err = bt->errc;
+    ka.sink.arg = bt->arg;
+    ka.sink.start = bt->start;
+    ka.sink.count = bt->count;
+    ka.sink.cap_end = std::max<uint64_t>(1, 2 * bt->out_cap);
+    ka.slow = bt->slow;
+    ka.stats = bt->stats;
+    ka.slow_ids = bt->d_slowlist;
+    ka.dbg = bt->dbg;
+    sx.rout = bt->rout;
+    sx.rstat = bt->rstat;
+    sx.rsel = bt->rsel;
+    sx.rnsel = bt->rnsel;
+    sx.scratch = bt->slow_scratch;
+    sx.slot_bytes = bt->slow_slot;
+    sx.grid = bt->slow_grid;
+    sx.lds_area = bt->slow_lds;
+    sx.lds_sort = bt->slow_sort;
+    // the large slice's capacity, lowered until the slices fit the device's LDS
+    top_cap = e->top_cap;
+    while (top_cap > 64 && kTopWaves * ((top_lds_bytes(s->Cp, top_cap) + 15) & ~(size_t)15) > e->max_lds) top_cap /= 2;
+    top_cap_small = std::min(e->top_cap_small, top_cap);
+    // (without class orders, k_select_top thresholds the votes by a histogram: KP_TOPK=0 keeps
+    // the full-candidate kernel there instead)
+    static const bool topk_on = kp_env_int("KP_TOPK", 1) != 0;
+    top = bits && e->top_on && s->Cp <= kTopMaxCp && (bt->d_ord != nullptr || (topk_on && bt->d_fb != nullptr)) &&
+          bt->n_all_dyn > 0 && kTopWaves * ((top_lds_bytes(s->Cp, top_cap) + 15) & ~(size_t)15) <= e->max_lds;
+    spread_orders = bits && e->top_on && bt->d_ord != nullptr && (!bt->l_cluster.empty() || !bt->l_region.empty()) &&
+                    kOrderWaves * ((order_lds_bytes(s->view.W, s->view.n_regions) + 15) & ~(size_t)15) <= e->max_lds &&
+                    kOrderWaves * ((region_a_order_lds_bytes(s->view.n_regions, s->view.W) + 15) & ~(size_t)15) <=
+                        e->max_lds;
+    orders = (top && bt->d_ord != nullptr) || spread_orders;
+    gate = !bt->l_region.empty();
+  }
   // A launch's KArgs copied to its own device slot (ordered before the launch on its
   // stream): the select kernels that keep pointers into their arguments read them there
   // (kp_launch.h SelectExtra::dargs). One slot per launch within this call.
-  int kslot = 0;
-  auto with_args = [&](const KArgs& k, dev::stream_t sq) -> SelectExtra {
+  SelectExtra with_args(const KArgs& k, dev::stream_t sq) {
     SelectExtra r = sx;
     if (kslot >= kArgSlots) return r;  // (dargs stays null: the launch reports EINVAL)
     bt->h_kargs[kslot] = k;
     if (dev::h2d(bt->d_kargs + kslot, bt->h_kargs + kslot, sizeof(KArgs), sq) == 0) r.dargs = bt->d_kargs + kslot;
     kslot++;
     return r;
-  };
+  }
+};
+
+// Stage 1, stream2: every row the selections read. The estimator classes' rows, the
+// component-set classes' rows, the other estimators' answers, k_filter and the out-of-tree
+// verdicts (or the pair kernel's per-binding rows instead), then the class orders; ev[4]
+// marks them complete, and stream waits for it.
+static int submit_rows(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int B = bt->B, fast = c.fast;
+  const bool bits = c.bits;
+  dev::stream_t st = e->stream, sp = e->stream2;
   HIPCHK(dev::event_record(e->ev[3], sp));
   // component-set classes (BF_SETS bindings): their class rows (after the estimator
   // classes' rows, before k_class_order reads them all), and in the pair-row mode those
@@ -3896,6 +3853,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
             dev::est_class(sp, s->view, bt->view, bt->d_crep, (int)bt->l_cls_single.size(), bt->cls_rows, fast,
                            bt->d_cls_single, bt->fmask));
   } else {
+    const int md_cap = md_cap_of(s);
     KPROF(sp, pair_name(fast), B, -1,
           dev::pair(sp, s->view, bt->view, nullptr, 0, B, bt->fmask, bt->est, nullptr, 0, md_cap, smem_pair(s, md_cap),
                     fast));
@@ -3906,41 +3864,18 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
       KPROF(sp, "k_filter_extra", bt->l_flt.size(), -1,
             dev::filter_extra(sp, s->view, bt->d_flt_list, (int)bt->l_flt.size(), bt->d_flt_rows, bt->fmask, bt->est));
     if (int rc = sets_rows()) return rc;
+    if (!bt->l_sets.empty())
+      KPROF(sp, "k_rows_from_class", bt->l_sets.size(), -1,
+            dev::rows_from_class(sp, s->view, bt->view, bt->d_sets_list, (int)bt->l_sets.size(), bt->d_bcls,
+                                 bt->cls_rows, bt->fmask, bt->est));
+    // the other estimators' answers merged over the rows of the bindings whose class has a
+    // row; the entries are cal_merge'd already (0 on infeasible clusters), and a
+    // GeneralEstimator answer is below MaxInt32, so the minimum is the reference's
+    if (!bt->l_est_cls.empty())
+      KPROF(sp, "k_est_extra", B, -1,
+            dev::est_extra(sp, s->Cp, nullptr, B, bt->d_bcls, bt->d_cls_est, bt->d_est_rows, bt->est));
   }
-  if (!bits && !bt->l_sets.empty())
-    KPROF(sp, "k_rows_from_class", bt->l_sets.size(), -1,
-          dev::rows_from_class(sp, s->view, bt->view, bt->d_sets_list, (int)bt->l_sets.size(), bt->d_bcls,
-                               bt->cls_rows, bt->fmask, bt->est));
-  // pair-row mode: the same merge over the rows of the bindings whose class has a row; the
-  // entries are cal_merge'd already (0 on infeasible clusters), and a GeneralEstimator
-  // answer is below MaxInt32, so the minimum is the reference's
-  if (!bits && !bt->l_est_cls.empty())
-    KPROF(sp, "k_est_extra", B, -1,
-          dev::est_extra(sp, s->Cp, nullptr, B, bt->d_bcls, bt->d_cls_est, bt->d_est_rows, bt->est));
-  // SEL_ALL DynamicWeight / Aggregated over the deciding candidates (kp_top.h): the
-  // class rows' orders first
-  // the large slice's capacity, lowered until the slices fit the device's LDS
-  int top_cap = e->top_cap;
-  while (top_cap > 64 && kTopWaves * ((top_lds_bytes(s->Cp, top_cap) + 15) & ~(size_t)15) > e->max_lds) top_cap /= 2;
-  const int top_cap_small = std::min(e->top_cap_small, top_cap);
-  // (without class orders, k_select_top thresholds the votes by a histogram: KP_TOPK=0 keeps
-  // the full-candidate kernel there instead)
-  static const bool topk_on = [] {
-    const char* v = getenv("KP_TOPK");
-    return !v || atoi(v) != 0;
-  }();
-  const bool top = bits && e->top_on && s->Cp <= kTopMaxCp && (bt->d_ord != nullptr || (topk_on && bt->d_fb != nullptr)) &&
-                   bt->n_all_dyn > 0 && kTopWaves * ((top_lds_bytes(s->Cp, top_cap) + 15) & ~(size_t)15) <= e->max_lds;
-  // class orders: k_select_top's walk, and the spread selections over them
-  // (k_spread_order, k_region_a_order), each where its LDS slices fit the device
-  const bool spread_orders = bits && e->top_on && bt->d_ord != nullptr &&
-                             (!bt->l_cluster.empty() || !bt->l_region.empty()) &&
-                             kOrderWaves * ((order_lds_bytes(s->view.W, s->view.n_regions) + 15) & ~(size_t)15) <=
-                                 e->max_lds &&
-                             kOrderWaves * ((region_a_order_lds_bytes(s->view.n_regions, s->view.W) + 15) & ~(size_t)15) <=
-                                 e->max_lds;
-  const bool orders = (top && bt->d_ord != nullptr) || spread_orders;
-  if (orders) {
+  if (c.orders) {
     // k_class_order reads only the class rows (k_est_class), so it runs on stream3 beside
     // k_filter and stream2 waits for it (profiled runs keep it on stream2: each kernel's
     // event time is then its own)
@@ -3956,20 +3891,22 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
   HIPCHK(dev::event_record(e->ev[4], sp));
   HIPCHK(dev::stream_wait(st, e->ev[4]));  // every pair row precedes the rest
   HIPCHK(dev::event_record(e->ev[1], st));
-  // The three selection kinds touch disjoint bindings: SEL_ALL on stream2 (after the
-  // pair kernel there), cluster spread on stream3, the region chain on stream, so a
-  // latency-bound kernel shares the CUs with the others instead of running alone.
+  return KP_OK;
+}
+
+// Stage 2, stream2: the SEL_ALL bindings. k_select_top's slices over [0, n_all_dyn) and
+// the full-candidate kernel over what they hand back, k_select_static, the streamed kernel
+// over the rest. ev[7] -> ev[8] times it.
+static int submit_sel_all(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const bool bits = c.bits, top = c.top;
+  const int cap = c.cap;
+  dev::stream_t sp = e->stream2;
   HIPCHK(dev::event_record(e->ev[7], sp));
-  // Fallback launches over device-appended lists, with a region chain (e->gate_fb): their
-  // counts are read back where the host synchronises anyway (the region chain, k_slow's
-  // count), so a list left empty launches nothing; the SEL_ALL and cluster-spread
-  // fallbacks move to stream3 after that read, before k_slow.
-  const bool gate = e->gate_fb != 0 && !bt->l_region.empty();
-  const bool gate_region = gate && e->gate_fb == 1;
-  bool defer_all = false, defer_all_stream = false, defer_cl = false;
-  KArgs f_def{}, cl_def{};
   if (!bt->l_all.empty()) {
-    KArgs k = ka;
+    KArgs k = c.ka;
     k.list = bt->d_all;
     k.n = (int)bt->l_all.size();
     // Candidates gathered into LDS (k_select_all), or, in bits mode, streamed from
@@ -3992,10 +3929,10 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
       // keep more waves per CU), then top_cap over the bindings whose subset outgrew it
       // (a device-appended list, grid-stride waves; the capacity only bounds the subset,
       // so both runs give the same answer)
-      const bool mid = e->top_cap_mid >= 64 && e->top_cap_mid < top_cap && !e->top_wg;
+      const bool mid = e->top_cap_mid >= 64 && e->top_cap_mid < c.top_cap;
       for (int part = 0; part < 2; part++) {
         KArgs g = k;
-        const int cap_p = part == 0 ? top_cap_small : (mid ? e->top_cap_mid : top_cap);
+        const int cap_p = part == 0 ? c.top_cap_small : (mid ? e->top_cap_mid : c.top_cap);
         g.list = bt->d_all + (part == 0 ? 0 : bt->n_top_small);
         g.lcls = bt->d_all_cls + (part == 0 ? 0 : bt->n_top_small);
         g.n = part == 0 ? bt->n_top_small : bt->n_all_dyn - bt->n_top_small;
@@ -4008,19 +3945,14 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
         const size_t slice = (top_lds_bytes(s->Cp, cap_p) + 15) & ~(size_t)15;
         dev::stream_t sx_ = split && part == 1 ? e->stream3 : sp;
         if (split && part == 1) HIPCHK(dev::stream_wait(sx_, e->ev[4]));
-        // the large-subset bindings: a workgroup each (wave 0 walks, the workgroup divides)
-        const size_t wg_lds = (top_wg_lds_bytes(s->Cp, cap_p) + 15) & ~(size_t)15;
-        if (part == 1 && e->top_wg && wg_lds <= e->max_lds)
-          KPROF(sx_, "k_select_top_wg", g.n, -1, dev::select_top_wg(sx_, g, ta, wg_lds));
-        else
-          KPROF(sx_, "k_select_top", g.n, -1, dev::select_top(sx_, g, ta, slice));
+        KPROF(sx_, "k_select_top", g.n, -1, dev::select_top(sx_, g, ta, slice));
         if (part == 1 && mid) {
           KArgs o = k;
           o.list = bt->d_ofb;
           o.n = g.n;  // (the list's capacity; its length is stats[16])
           o.n_dev = bt->stats + 16;
-          TopArgs tb{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + 9, top_cap};
-          const size_t slice_l = (top_lds_bytes(s->Cp, top_cap) + 15) & ~(size_t)15;
+          TopArgs tb{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + 9, c.top_cap};
+          const size_t slice_l = (top_lds_bytes(s->Cp, c.top_cap) + 15) & ~(size_t)15;
           // (units 0: the launch re-runs bindings the kernel's units already count)
           KPROF(sx_, "k_select_top", 0, -1, dev::select_top(sx_, o, tb, slice_l, kTopOverGrid));
         }
@@ -4034,21 +3966,21 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
       f.list = bt->d_fb;
       f.n = bt->n_all_dyn;
       f.n_dev = bt->stats + 9;
-      if (gate) {
-        f_def = f;
-        defer_all = true;
-        defer_all_stream = stream_all;
+      if (c.gate) {
+        c.f_def = f;
+        c.defer_all = true;
+        c.defer_all_stream = stream_all;
       } else if (stream_all) {
-        const SelectExtra sxa1 = with_args(f, sp);  // (the slot is copied before the launch is timed)
+        const SelectExtra sxa1 = c.with_args(f, sp);  // (the slot is copied before the launch is timed)
         KPROF(sp, "k_select_all_stream", 0, 9,
               dev::select(sp, SEL_LAUNCH_ALL_STREAM, f, sel_stream_lds_bytes(s->Cp), cap, sxa1));
       } else {
-        KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), 0, 9, dev::select(sp, SEL_LAUNCH_ALL, f, smem_all(s), cap, sx));
+        KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), 0, 9, dev::select(sp, SEL_LAUNCH_ALL, f, smem_all(s), cap, c.sx));
       }
     } else if (na > 0) {
       KArgs g = k;
       g.n = na;
-      KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), g.n, -1, dev::select(sp, SEL_LAUNCH_ALL, g, smem_all(s), cap, sx));
+      KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), g.n, -1, dev::select(sp, SEL_LAUNCH_ALL, g, smem_all(s), cap, c.sx));
     }
     // the rest: StaticWeight at class level (k_select_static) where it applies, then
     // the streamed kernel
@@ -4065,198 +3997,219 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
       KArgs g = k;
       g.list = bt->d_all + rest0;
       g.n = k.n - rest0;
-      {  // (the argument slot is copied before the launch is timed)
-        const SelectExtra sxa2 = with_args(g, sp);
-        KPROF(sp, "k_select_all_stream", g.n, -1,
-              dev::select(sp, SEL_LAUNCH_ALL_STREAM, g, sel_stream_lds_bytes(s->Cp), cap, sxa2));
-      }
+      // (the argument slot is copied before the launch is timed)
+      const SelectExtra sxa2 = c.with_args(g, sp);
+      KPROF(sp, "k_select_all_stream", g.n, -1,
+            dev::select(sp, SEL_LAUNCH_ALL_STREAM, g, sel_stream_lds_bytes(s->Cp), cap, sxa2));
     }
   }
   HIPCHK(dev::event_record(e->ev[8], sp));  // k_select_all alone: ev[7] -> ev[8]
+  return KP_OK;
+}
+
+// Stage 3, stream3 (behind the rows, ev[4]): the cluster-spread bindings, over the class
+// orders first where the batch has them. ev[14] -> ev[15] times it.
+static int submit_cluster_spread(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int cap = c.cap;
   dev::stream_t s3 = e->stream3;
   HIPCHK(dev::stream_wait(s3, e->ev[4]));
-  if (!bt->l_cluster.empty()) {
-    KArgs k = ka;
-    k.list = bt->d_cluster;
-    k.n = (int)bt->l_cluster.size();
-    HIPCHK(dev::event_record(e->ev[14], s3));
-    if (spread_orders) {
-      // the class-order selection, one wave per binding; what it hands back runs below
-      k.ord = bt->d_ord;
-      k.cok = bt->d_cok;
-      k.n_order = bt->stats + 10;
-      OrderArgs oa{nullptr, nullptr, nullptr, bt->d_fbc, bt->stats + 12, 0};
-      KPROF(s3, "k_spread_order", k.n, -1,
-            dev::spread_order(s3, k, oa, (order_lds_bytes(s->view.W, s->view.n_regions) + 15) & ~(size_t)15));
-      k.sub = bt->d_fbc;
-      k.n_dev = bt->stats + 12;
-    }
-    if (gate && k.n_dev) {
-      cl_def = k;
-      defer_cl = true;
-    } else {  // (the argument slot is copied before the launch is timed)
-      const SelectExtra sxa3 = with_args(k, s3);
-      KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 12 : -1,
-            dev::select(s3, SEL_LAUNCH_CLUSTER, k, smem_cluster(s, cap), cap, sxa3));
-    }
-    HIPCHK(dev::event_record(e->ev[15], s3));
+  if (bt->l_cluster.empty()) return KP_OK;
+  KArgs k = c.ka;
+  k.list = bt->d_cluster;
+  k.n = (int)bt->l_cluster.size();
+  HIPCHK(dev::event_record(e->ev[14], s3));
+  if (c.spread_orders) {
+    // the class-order selection, one wave per binding; what it hands back runs below
+    k.ord = bt->d_ord;
+    k.cok = bt->d_cok;
+    k.n_order = bt->stats + 10;
+    OrderArgs oa{nullptr, nullptr, nullptr, bt->d_fbc, bt->stats + 12, 0};
+    KPROF(s3, "k_spread_order", k.n, -1,
+          dev::spread_order(s3, k, oa, (order_lds_bytes(s->view.W, s->view.n_regions) + 15) & ~(size_t)15));
+    k.sub = bt->d_fbc;
+    k.n_dev = bt->stats + 12;
   }
-  // k_slow after every kernel that flags bindings (SEL_ALL on stream2, cluster spread
-  // here; the region chain flags none), so it runs beside the region chain
-  double th0 = 0, th1 = 0;
-  if (!bt->l_region.empty()) {
-    const int nr = (int)bt->l_region.size(), R = s->view.n_regions;
-    KArgs k = ka;
-    k.list = bt->d_region;
-    k.n = nr;
-    if (spread_orders) {  // region_b_by_order
-      k.ord = bt->d_ord;
-      k.cok = bt->d_cok;
-      k.n_order = bt->stats + 11;
+  if (c.gate && k.n_dev) {
+    c.cl_def = k;
+    c.defer_cl = true;
+  } else {  // (the argument slot is copied before the launch is timed)
+    const SelectExtra sxa3 = c.with_args(k, s3);
+    KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 12 : -1,
+          dev::select(s3, SEL_LAUNCH_CLUSTER, k, smem_cluster(s, cap), cap, sxa3));
+  }
+  HIPCHK(dev::event_record(e->ev[15], s3));
+  return KP_OK;
+}
+
+// Stage 4, stream: the region chain. Stage A (over the class orders, then the rest),
+// selectGroups on the device with its host step, stage B the same two ways, k_region_wide.
+// The two fallback launches over device-appended lists read their counts back first (the
+// grid is then sized by the count: spread_grid), so an empty list launches nothing.
+static int submit_region_chain(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int cap = c.cap;
+  dev::stream_t st = e->stream;
+  if (bt->l_region.empty()) return KP_OK;
+  const int nr = (int)bt->l_region.size(), R = s->view.n_regions;
+  KArgs k = c.ka;
+  k.list = bt->d_region;
+  k.n = nr;
+  if (c.spread_orders) {  // region_b_by_order
+    k.ord = bt->d_ord;
+    k.cok = bt->d_cok;
+    k.n_order = bt->stats + 11;
+  }
+  if (c.spread_orders) {  // stage A of the order-eligible bindings, one wave each; the rest below
+    KArgs ko = k;
+    ko.n_order = nullptr;
+    KPROF(st, "k_region_a_order", ko.n, -1, dev::region_a_order(st, ko, bt->rout, bt->rstat, bt->d_fba, bt->stats + 14,
+                               (region_a_order_lds_bytes(R, s->view.W) + 15) & ~(size_t)15));
+    KArgs kf = k;
+    kf.sub = bt->d_fba;
+    kf.n_dev = bt->stats + 14;
+    uint32_t nfa = 0;
+    HIPCHK(dev::d2h(&nfa, bt->stats + 14, 4, st));
+    HIPCHK(dev::sync(st));
+    if (nfa > 0) {  // (the argument slot is copied before the launch is timed)
+      SelectExtra sxa4 = c.with_args(kf, st);
+      sxa4.list_grid = (int)nfa;
+      KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), 0, 14,
+            dev::select(st, SEL_LAUNCH_REGION_A, kf, smem_region_a(s), cap, sxa4));
     }
-    if (spread_orders) {  // stage A of the order-eligible bindings, one wave each; the rest below
-      KArgs ko = k;
-      ko.n_order = nullptr;
-      KPROF(st, "k_region_a_order", ko.n, -1, dev::region_a_order(st, ko, bt->rout, bt->rstat, bt->d_fba, bt->stats + 14,
-                                 (region_a_order_lds_bytes(R, s->view.W) + 15) & ~(size_t)15));
-      KArgs kf = k;
-      kf.sub = bt->d_fba;
-      kf.n_dev = bt->stats + 14;
-      uint32_t nfa = 1;
-      if (gate_region) {  // (the grid is then sized by the count: spread_grid)
-        HIPCHK(dev::d2h(&nfa, bt->stats + 14, 4, st));
-        HIPCHK(dev::sync(st));
-      }
-      if (nfa > 0) {  // (the argument slot is copied before the launch is timed)
-        SelectExtra sxa4 = with_args(kf, st);
-        if (gate_region) sxa4.list_grid = (int)nfa;
-        KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), 0, 14,
-              dev::select(st, SEL_LAUNCH_REGION_A, kf, smem_region_a(s), cap, sxa4));
-      }
-    } else {
-      {  // (the argument slot is copied before the launch is timed)
-        const SelectExtra sxa5 = with_args(k, st);
-        KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), k.n, -1,
-              dev::select(st, SEL_LAUNCH_REGION_A, k, smem_region_a(s), cap, sxa5));
-      }
-    }
-    // selectGroups: on the device (one thread per binding) unless the snapshot
-    // has more regions than its arrays hold; bindings whose DFS exceeds the node
-    // budget, and every binding on the other route, take the host DFS.
-    const bool dev_groups = R <= kGroupMax && !getenv("KP_REGION_HOST");
-    uint32_t nh = 0;
+  } else {  // (the argument slot is copied before the launch is timed)
+    const SelectExtra sxa5 = c.with_args(k, st);
+    KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), k.n, -1,
+          dev::select(st, SEL_LAUNCH_REGION_A, k, smem_region_a(s), cap, sxa5));
+  }
+  // selectGroups: on the device (one thread per binding) unless the snapshot
+  // has more regions than its arrays hold; bindings whose DFS exceeds the node
+  // budget, and every binding on the other route, take the host DFS.
+  const bool dev_groups = R <= kGroupMax && !kp_env_flag("KP_REGION_HOST");
+  uint32_t nh = 0;
+  if (dev_groups) {
+    HIPCHK(dev::fill(bt->nhost, 0, 4, st));
+    KPROF(st, "k_region_groups", nr, -1, dev::region_groups(st, bt->rout, bt->rstat, bt->view.hdr, bt->d_region, nr, R, bt->rsel, bt->rnsel,
+                              bt->nhost));
+    HIPCHK(dev::d2h(&nh, bt->nhost, 4, st));
+    HIPCHK(dev::sync(st));
+  }
+  if (!dev_groups || nh > 0) {
+    bt->h_rout.resize((size_t)nr * std::max(R, 1));
+    bt->h_rstat.resize(nr);
+    HIPCHK(dev::d2h(bt->h_rout.data(), bt->rout, sizeof(RegionOut) * bt->h_rout.size(), st));
+    HIPCHK(dev::d2h(bt->h_rstat.data(), bt->rstat, 4 * nr, st));
+    bt->h_rsel.assign((size_t)nr * std::max(R, 1), -1);
+    bt->h_rnsel.assign(nr, 0);
     if (dev_groups) {
-      HIPCHK(dev::fill(bt->nhost, 0, 4, st));
-      KPROF(st, "k_region_groups", nr, -1, dev::region_groups(st, bt->rout, bt->rstat, bt->view.hdr, bt->d_region, nr, R, bt->rsel, bt->rnsel,
-                                bt->nhost));
-      HIPCHK(dev::d2h(&nh, bt->nhost, 4, st));
-      HIPCHK(dev::sync(st));
+      HIPCHK(dev::d2h(bt->h_rsel.data(), bt->rsel, 4 * bt->h_rsel.size(), st));
+      HIPCHK(dev::d2h(bt->h_rnsel.data(), bt->rnsel, 4 * nr, st));
     }
-    if (!dev_groups || nh > 0) {
-      bt->h_rout.resize((size_t)nr * std::max(R, 1));
-      bt->h_rstat.resize(nr);
-      HIPCHK(dev::d2h(bt->h_rout.data(), bt->rout, sizeof(RegionOut) * bt->h_rout.size(), st));
-      HIPCHK(dev::d2h(bt->h_rstat.data(), bt->rstat, 4 * nr, st));
-      bt->h_rsel.assign((size_t)nr * std::max(R, 1), -1);
-      bt->h_rnsel.assign(nr, 0);
-      if (dev_groups) {
-        HIPCHK(dev::d2h(bt->h_rsel.data(), bt->rsel, 4 * bt->h_rsel.size(), st));
-        HIPCHK(dev::d2h(bt->h_rnsel.data(), bt->rnsel, 4 * nr, st));
+    HIPCHK(dev::sync(st));
+    c.th0 = now_ms();
+    parallel_for(nr, e->n_threads, [&](int j) {
+      if (dev_groups && bt->h_rnsel[j] != kGroupsHost) return;
+      if (bt->h_rstat[j] != 0) {
+        bt->h_rnsel[j] = -1000;
+        return;
       }
-      HIPCHK(dev::sync(st));
-      th0 = now_ms();
-      parallel_for(nr, e->n_threads, [&](int j) {
-        if (dev_groups && bt->h_rnsel[j] != kGroupsHost) return;
-        if (bt->h_rstat[j] != 0) {
-          bt->h_rnsel[j] = -1000;
-          return;
-        }
-        const BindHdr& h = bt->hdr[bt->l_region[j]];
-        std::vector<G> groups;
-        for (int r = 0; r < R; r++) {
-          const RegionOut& ro = bt->h_rout[(size_t)j * R + r];
-          if (ro.count > 0) groups.push_back({r, ro.count, ro.score});
-        }
-        // selectBestClustersByRegion (select_clusters_by_region.go:25-40)
-        if ((int64_t)groups.size() < h.region_min) {
-          bt->h_rnsel[j] = -KP_ERR_REGION_MIN_GROUPS;
-          return;
-        }
-        auto sel = select_groups(groups, h.region_min, h.region_max, h.cluster_min);
-        if (sel.empty()) {
-          bt->h_rnsel[j] = -KP_ERR_REGION_CLUSTER_MIN;
-          return;
-        }
-        for (int r = 0; r < R; r++) bt->h_rsel[(size_t)j * R + r] = -1;
-        for (size_t q = 0; q < sel.size(); q++) bt->h_rsel[(size_t)j * R + q] = sel[q];
-        bt->h_rnsel[j] = (int32_t)sel.size();
-      });
-      th1 = now_ms();
-      HIPCHK(dev::h2d(bt->rsel, bt->h_rsel.data(), 4 * bt->h_rsel.size(), st));
-      HIPCHK(dev::h2d(bt->rnsel, bt->h_rnsel.data(), 4 * nr, st));
-    }
-    if (spread_orders) {
-      OrderArgs oa{bt->rout, bt->rsel, bt->rnsel, bt->d_fbr, bt->stats + 13, 1};
-      KPROF(st, "k_spread_order", k.n, -1, dev::spread_order(st, k, oa, (order_lds_bytes(s->view.W, R) + 15) & ~(size_t)15));
-      k.sub = bt->d_fbr;
-      k.n_dev = bt->stats + 13;
-    }
-    uint32_t nfb = 1;
-    if (gate_region && k.n_dev) {
-      HIPCHK(dev::d2h(&nfb, bt->stats + 13, 4, st));
-      HIPCHK(dev::sync(st));
-    }
-    if (nfb > 0) {  // (the argument slot is copied before the launch is timed)
-      SelectExtra sxa6 = with_args(k, st);
-      if (gate_region && k.n_dev) sxa6.list_grid = (int)nfb;
-      KPROF(st, sel_name(SEL_LAUNCH_REGION_B, smem_region_b(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 13 : -1,
-            dev::select(st, SEL_LAUNCH_REGION_B, k, smem_region_b(s, cap), cap, sxa6));
-    }
-    // the selections past k_region_b's lists (marked there in a.slow), queued behind it: no
-    // count is read back, a workgroup whose binding carries no mark returns at once
-    if (!bt->l_region_wide.empty()) {
-      KArgs kw = ka;
-      kw.list = bt->d_region;
-      kw.n = nr;
-      const SelectExtra sxw = with_args(kw, st);
-      KPROF(st, "k_region_wide", 0, 17,
-            dev::region_wide(st, kw, sxw, bt->d_region_wide, (int)bt->l_region_wide.size(), bt->wide_scratch,
-                             bt->wide_slot, bt->wide_grid, bt->slow_cap, bt->wide_sort, bt->stats + 17));
-    }
+      const BindHdr& h = bt->hdr[bt->l_region[j]];
+      std::vector<G> groups;
+      for (int r = 0; r < R; r++) {
+        const RegionOut& ro = bt->h_rout[(size_t)j * R + r];
+        if (ro.count > 0) groups.push_back({r, ro.count, ro.score});
+      }
+      // selectBestClustersByRegion (select_clusters_by_region.go:25-40)
+      if ((int64_t)groups.size() < h.region_min) {
+        bt->h_rnsel[j] = -KP_ERR_REGION_MIN_GROUPS;
+        return;
+      }
+      auto sel = select_groups(groups, h.region_min, h.region_max, h.cluster_min);
+      if (sel.empty()) {
+        bt->h_rnsel[j] = -KP_ERR_REGION_CLUSTER_MIN;
+        return;
+      }
+      for (int r = 0; r < R; r++) bt->h_rsel[(size_t)j * R + r] = -1;
+      for (size_t q = 0; q < sel.size(); q++) bt->h_rsel[(size_t)j * R + q] = sel[q];
+      bt->h_rnsel[j] = (int32_t)sel.size();
+    });
+    c.th1 = now_ms();
+    HIPCHK(dev::h2d(bt->rsel, bt->h_rsel.data(), 4 * bt->h_rsel.size(), st));
+    HIPCHK(dev::h2d(bt->rnsel, bt->h_rnsel.data(), 4 * nr, st));
   }
-  // k_slow after every kernel that flags bindings (SEL_ALL on stream2, cluster spread on
-  // stream3; the region chain, queued above, flags none), beside the region chain. With a
-  // region chain the flagged count is read back first (the host waits for the flagging
-  // kernels only): a batch that flags none launches nothing, and a few flagged take a
-  // small grid, instead of up to 256 workgroups whose LDS slices wait for CUs behind the
-  // region kernels (config 4: 3.87 -> 3.74 ms). Without one the wait costs more than it
-  // saves (config 3: 2.00 -> 2.20 ms with four batches in flight), so k_slow is queued.
+  uint32_t nfb = 1;
+  if (c.spread_orders) {
+    OrderArgs oa{bt->rout, bt->rsel, bt->rnsel, bt->d_fbr, bt->stats + 13, 1};
+    KPROF(st, "k_spread_order", k.n, -1, dev::spread_order(st, k, oa, (order_lds_bytes(s->view.W, R) + 15) & ~(size_t)15));
+    k.sub = bt->d_fbr;
+    k.n_dev = bt->stats + 13;
+    HIPCHK(dev::d2h(&nfb, bt->stats + 13, 4, st));
+    HIPCHK(dev::sync(st));
+  }
+  if (nfb > 0) {  // (the argument slot is copied before the launch is timed)
+    SelectExtra sxa6 = c.with_args(k, st);
+    if (k.n_dev) sxa6.list_grid = (int)nfb;
+    KPROF(st, sel_name(SEL_LAUNCH_REGION_B, smem_region_b(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 13 : -1,
+          dev::select(st, SEL_LAUNCH_REGION_B, k, smem_region_b(s, cap), cap, sxa6));
+  }
+  // the selections past k_region_b's lists (marked there in a.slow), queued behind it: no
+  // count is read back, a workgroup whose binding carries no mark returns at once
+  if (!bt->l_region_wide.empty()) {
+    KArgs kw = c.ka;
+    kw.list = bt->d_region;
+    kw.n = nr;
+    const SelectExtra sxw = c.with_args(kw, st);
+    KPROF(st, "k_region_wide", 0, 17,
+          dev::region_wide(st, kw, sxw, bt->d_region_wide, (int)bt->l_region_wide.size(), bt->wide_scratch,
+                           bt->wide_slot, bt->wide_grid, bt->slow_cap, bt->wide_sort, bt->stats + 17));
+  }
+  return KP_OK;
+}
+
+// Stage 5, stream3: k_slow after every kernel that flags bindings (SEL_ALL on stream2,
+// cluster spread on stream3; the region chain, queued above, flags none), beside the region
+// chain. With a region chain the flagged count is read back first (the host waits for the
+// flagging kernels only): a batch that flags none launches nothing, and a few flagged take a
+// small grid, instead of up to 256 workgroups whose LDS slices wait for CUs behind the
+// region kernels (config 4: 3.87 -> 3.74 ms); the deferred SEL_ALL and cluster-spread
+// fallbacks run at the same read. Without one the wait costs more than it saves (config 3:
+// 2.00 -> 2.20 ms with four batches in flight), so k_slow is queued.
+static int submit_slow(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int cap = c.cap;
+  dev::stream_t s3 = e->stream3;
   HIPCHK(dev::stream_wait(s3, e->ev[8]));
   uint32_t nslow = (uint32_t)bt->slow_grid;
-  if (!bt->l_region.empty() && (gate || !bt->l_slow.empty())) {
+  if (c.gate) {
     uint32_t hs[16];  // (stats [0] flagged, [9] SEL_ALL fallbacks, [12] cluster-spread fallbacks)
     HIPCHK(dev::d2h(hs, bt->stats, sizeof(hs), s3));
     HIPCHK(dev::sync(s3));
     nslow = hs[0];
     bool more = false;  // a deferred fallback runs: it may flag bindings for k_slow
-    if (defer_all && hs[9] > 0) {
-      const KArgs& f = f_def;
-      if (defer_all_stream) {
-        SelectExtra sxa1 = with_args(f, s3);
+    if (c.defer_all && hs[9] > 0) {
+      const KArgs& f = c.f_def;
+      if (c.defer_all_stream) {
+        SelectExtra sxa1 = c.with_args(f, s3);
         sxa1.list_grid = (int)hs[9];
         KPROF(s3, "k_select_all_stream", hs[9], -1,
               dev::select(s3, SEL_LAUNCH_ALL_STREAM, f, sel_stream_lds_bytes(s->Cp), cap, sxa1));
       } else {
-        SelectExtra sxg = sx;
+        SelectExtra sxg = c.sx;
         sxg.list_grid = (int)hs[9];
         KPROF(s3, sel_name(SEL_LAUNCH_ALL, smem_all(s)), hs[9], -1,
               dev::select(s3, SEL_LAUNCH_ALL, f, smem_all(s), cap, sxg));
       }
       more = true;
     }
-    if (defer_cl && hs[12] > 0) {
-      const KArgs& k = cl_def;
-      SelectExtra sxa3 = with_args(k, s3);
+    if (c.defer_cl && hs[12] > 0) {
+      const KArgs& k = c.cl_def;
+      SelectExtra sxa3 = c.with_args(k, s3);
       sxa3.list_grid = (int)hs[12];
       KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), hs[12], -1,
             dev::select(s3, SEL_LAUNCH_CLUSTER, k, smem_cluster(s, cap), cap, sxa3));
@@ -4265,54 +4218,50 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
     if (more) nslow = (uint32_t)bt->slow_grid;  // (the kernel reads the final count itself)
   }
   if (!bt->l_slow.empty() && nslow > 0) {
-    KArgs k = ka;
+    KArgs k = c.ka;
     k.list = bt->d_slowlist;
     k.n = (int)bt->l_slow.size();
-    k.ord = orders ? bt->d_ord : nullptr;  // sortClusters order from the class orders (kp_kernels.h)
-    k.cok = orders ? bt->d_cok : nullptr;
+    k.ord = c.orders ? bt->d_ord : nullptr;  // sortClusters order from the class orders (kp_kernels.h)
+    k.cok = c.orders ? bt->d_cok : nullptr;
     if (!e->slow_order) k.ord = nullptr;
-    SelectExtra sxs = with_args(k, s3);
+    SelectExtra sxs = c.with_args(k, s3);
     sxs.grid = (int)std::min<uint32_t>((uint32_t)bt->slow_grid, nslow);
     KPROF(s3, "k_slow", 0, 0,
           dev::select(s3, SEL_LAUNCH_SLOW, k,
-                      kRedBytes + 512 + 4 * (size_t)(((s->Cp + 31) >> 5) + 4) + sx.lds_area + sx.lds_sort,
+                      kRedBytes + 512 + 4 * (size_t)(((s->Cp + 31) >> 5) + 4) + c.sx.lds_area + c.sx.lds_sort,
                       bt->slow_cap, sxs));
   }
   HIPCHK(dev::event_record(e->ev[9], s3));
+  return KP_OK;
+}
+
+// Stage 6, stream (behind every select kernel and k_slow): results -> host. The offsets
+// are scanned and the results compacted to CSR on the device (or packed: one word per
+// target into cidx_d, the escape counts scanned into wide_offsets — the CSR scan's chunk
+// totals are consumed by now, one stream — and the escaped replicas into crep_d); the
+// per-binding arrays are read back here, the CSR by schedule_finish once it knows its size.
+static int submit_results(SubmitCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int B = bt->B;
+  dev::stream_t st = e->stream;
   HIPCHK(dev::stream_wait(st, e->ev[8]));
   HIPCHK(dev::stream_wait(st, e->ev[9]));  // k_slow (stream3) and every select kernel precede the results
   HIPCHK(dev::event_record(e->ev[2], st));
-  // results -> host, compacted to CSR: offsets scanned and results compacted on
-  // the device, then the per-binding arrays and the CSR copied back
   KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->count, B, bt->offsets_d, bt->off_part));
-  // With page-locked result buffers from an earlier call (their capacity known before the
-  // launch), k_compact also writes the CSR straight into them over the bus (e->zc): the
-  // call then needs no host round trip for the CSR's size and no copy after it, so an
-  // engine's stream stays queued to its end (several engines in flight no longer idle the
-  // GPU while each one reads its total back). A total past the capacity takes the copy.
-  uint32_t* zc_idx = nullptr;
-  int32_t* zc_rep = nullptr;
-  if (packed) {
-    // the packed form: one word per target into cidx_d, the escape counts scanned into
-    // wide_offsets (the CSR scan's chunk totals are consumed by now: one stream), the
-    // escaped replicas into crep_d; the zero-copy and speculative-copy paths stay wide-only
+  if (c.packed) {
     KPROF(st, "k_pack", B, -1,
           dev::pack(st, bt->start, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->wcount_d, B, s->view.perm));
     KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->wcount_d, B, bt->woff_d, bt->off_part));
     KPROF(st, "k_pack_wide", B, -1,
           dev::pack_wide(st, bt->start, bt->offsets_d, bt->woff_d, bt->out_rep, bt->crep_d, B));
     HIPCHK(dev::d2h(bt->h_woff, bt->woff_d, 8 * (size_t)(B + 1), st));
-  } else if (e->zc && bt->h_cidx && bt->h_crep && bt->h_res_cap > 0) {
-    void *di = nullptr, *dr = nullptr;
-    if (dev::host_device_ptr(bt->h_cidx, &di) == 0 && dev::host_device_ptr(bt->h_crep, &dr) == 0) {
-      zc_idx = (uint32_t*)di;
-      zc_rep = (int32_t*)dr;
-    }
-  }
-  if (!packed)
+  } else {
     KPROF(st, "k_compact", B, -1,
           dev::compact(st, bt->start, bt->count, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->crep_d, B,
-                       s->view.perm, zc_idx, zc_rep, zc_idx ? bt->h_res_cap : 0));
+                       s->view.perm));
+  }
   bt->h_status.resize(B);
   bt->h_err.resize(B);
   bt->h_arg.resize(B);
@@ -4322,31 +4271,75 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
   HIPCHK(dev::d2h(bt->h_arg.data(), bt->arg, 8 * (size_t)B, st));
   HIPCHK(dev::d2h(bt->h_offsets.data(), bt->offsets_d, 8 * (size_t)(B + 1), st));
   HIPCHK(dev::d2h(bt->h_stats, bt->stats, sizeof(bt->h_stats), st));
-  pd.zc = zc_idx != nullptr;
-  pd.bits = bits;
-  pd.fast = fast;
-  pd.top = top;
-  pd.spread_orders = spread_orders;
-  pd.th0 = th0;
-  pd.th1 = th1;
-  // A batch scheduled again copies its previous call's CSR size ahead of the read-back of
-  // this call's total (the rest, if this total is larger, after it): one host round trip
-  // per call instead of two, so the stream has the copy queued behind the kernels.
-  uint64_t spec = 0;
-  if (!packed && !zc_idx && bt->h_cidx && bt->h_crep && e->spec_copy) {
-    spec = std::min<uint64_t>(bt->last_tot, bt->h_res_cap);
-    if (spec) {
-      HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * spec, st));
-      HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * spec, st));
-    }
-  }
-  pd.spec = spec;
+  SchedPend& pd = bt->pend;
   if (!pd.ev && dev::event_create(&pd.ev)) {
     pd.ev = nullptr;
     e->err = "kp_schedule_batch: event";
     return KP_EDEVICE;
   }
   HIPCHK(dev::event_record(pd.ev, st));
+  return KP_OK;
+}
+
+static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
+  if (!e || !bt) return KP_EINVAL;
+  if (int rc = refuse_out_of_tree(e, bt->snap, bt->flt_plugins)) return rc;
+  (void)dev::set_device(e->device);
+  kp_snapshot* s = bt->snap;
+  if (packed && s->C > 65536) {  // (kp_batch_create's LDS bound refuses such snapshots long before)
+    e->err = "kp_schedule_batch_packed: a packed cluster index holds 16 bits (more than 65536 clusters)";
+    return KP_ENOTSUP;
+  }
+  if (packed && ensure_packed(e, bt)) return KP_EDEVICE;
+  SchedPend& pd = bt->pend;
+  {
+    const dev::event_t ev = pd.ev;  // (the event is kept across calls)
+    pd = SchedPend{};
+    pd.ev = ev;
+  }
+  pd.packed = packed;
+  pd.t0 = now_ms();
+  pd.seq = ++e->submit_seq;
+  if (bt->B == 0) {
+    pd.empty = true;
+    pd.live = true;
+    return KP_OK;
+  }
+  if (!bt->l_region.empty() && s->view.n_regions != bt->n_regions) {
+    e->err = "kp_schedule_batch: the snapshot's region set changed since the batch was packed (re-create it)";
+    return KP_ESTATE;
+  }
+  if (batch_lds_check(e, s, bt)) return KP_ENOTSUP;
+  e->pk.clear();
+  dev::stream_t st = e->stream;
+  HIPCHK(dev::h2d(bt->counter, &bt->out_cap, sizeof(unsigned long long), st));  // the shared area's start
+  HIPCHK(dev::fill(bt->stats, 0, sizeof(bt->h_stats), st));
+  if (!bt->sets_cls.empty()) HIPCHK(dev::fill(bt->d_sets_ovf, 0, 4 * bt->sets_cls.size(), st));
+#if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
+  HIPCHK(dev::fill(bt->dbg, 0, kDbgSlots * kDbgSpread * 8, st));
+#endif
+  HIPCHK(dev::event_record(e->ev[0], st));
+  HIPCHK(dev::stream_wait(e->stream2, e->ev[0]));  // the fills above precede every kernel
+  SubmitCtx c(e, bt, packed);
+  if (!c.bits) {
+    if (ensure_rows(e, bt)) return KP_EDEVICE;
+    c.ka.est = bt->est;
+  }
+  // The three selection kinds touch disjoint bindings: SEL_ALL on stream2 (after the
+  // rows there), cluster spread on stream3, the region chain on stream, so a
+  // latency-bound kernel shares the CUs with the others instead of running alone.
+  if (int rc = submit_rows(c)) return rc;
+  if (int rc = submit_sel_all(c)) return rc;
+  if (int rc = submit_cluster_spread(c)) return rc;
+  if (int rc = submit_region_chain(c)) return rc;
+  if (int rc = submit_slow(c)) return rc;
+  if (int rc = submit_results(c)) return rc;
+  pd.bits = c.bits;
+  pd.fast = c.fast;
+  pd.top = c.top;
+  pd.spread_orders = c.spread_orders;
+  pd.th0 = c.th0;
+  pd.th1 = c.th1;
   pd.live = true;
   return KP_OK;
 }
@@ -4385,8 +4378,6 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   const double t0 = pd.t0, th0 = pd.th0, th1 = pd.th1;
   const bool bits = pd.bits, top = pd.top, spread_orders = pd.spread_orders;
   const int fast = pd.fast;
-  const uint64_t spec = pd.spec;
-  const bool zc = pd.zc;
   kp_stage_times tm{};
   HIPCHK(dev::event_sync(pd.ev));
   std::vector<uint32_t> sets_ovf(bt->sets_cls.size(), 0);
@@ -4396,12 +4387,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   }
   double tc0 = now_ms();
   const uint64_t tot = bt->h_offsets[B];
-  bool copy = !zc;  // (written by k_compact unless the total outgrew the buffers)
-  uint64_t have = zc ? tot : spec;  // entries already in the page-locked buffers
-  bt->last_tot = tot;
   if (tot > bt->h_res_cap || !bt->h_cidx) {
-    copy = true;
-    have = 0;
     buf_pool().put(-1, bt->h_cidx, bt->h_cidx_bytes);
     buf_pool().put(-1, bt->h_crep, bt->h_crep_bytes);
     bt->h_cidx = nullptr;
@@ -4417,15 +4403,15 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     bt->h_res_cap = std::min(bt->h_cidx_bytes, bt->h_crep_bytes) / 4;
   }
   // (a packed call: tot packed words in cidx_d and the n_wide <= tot escaped replicas in
-  // crep_d, 4 * (tot + n_wide) bytes instead of 8 * tot; submitted with zc and spec off)
+  // crep_d, 4 * (tot + n_wide) bytes instead of 8 * tot)
   uint64_t n_wide = packed ? bt->h_woff[B] : 0;
   if (packed) {
     if (tot) HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * tot, st));
     if (n_wide) HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * n_wide, st));
     if (tot) HIPCHK(dev::sync(st));
-  } else if (copy && tot > have) {
-    HIPCHK(dev::d2h(bt->h_cidx + have, bt->cidx_d + have, 4 * (tot - have), st));
-    HIPCHK(dev::d2h(bt->h_crep + have, bt->crep_d + have, 4 * (tot - have), st));
+  } else if (tot) {
+    HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * tot, st));
+    HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * tot, st));
     HIPCHK(dev::sync(st));
   }
   // A component-set class whose simulation outgrew the device's node runs in some
@@ -4507,7 +4493,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     fprintf(stderr, "\n");
   }
 #endif
-  if (getenv("KP_DEBUG_SLOW"))
+  if (kp_env_flag("KP_DEBUG_SLOW"))
     fprintf(stderr,
             "kp slow: total %u overflow/dup %u scale-down %u wrap %u tie %u weight %u cluster %u "
             "(ties resolved block-parallel %u); class-order spread fallbacks: cluster %u region %u (stage A %u)"
@@ -4618,7 +4604,7 @@ static int filter_batch_impl(kp_engine* e, kp_batch* bt, uint64_t* out_mask) {
   (void)dev::set_device(e->device);
   kp_snapshot* s = bt->snap;
   if (bt->B == 0) return KP_OK;
-  if (s->view.n_bits > 0 && !getenv("KP_PAIR_ROWS")) {  // the schedule path's bitset filter
+  if (s->view.n_bits > 0 && !kp_env_flag("KP_PAIR_ROWS")) {  // the schedule path's bitset filter
     HIPCHK(dev::filter(e->stream, s->view, bt->view, bt->fmask));
   } else {
     int rc = run_pair(e, bt, nullptr, 0, 0, bt->B);
@@ -4649,8 +4635,7 @@ static int filter_reasons_impl(kp_engine* e, kp_batch* bt, uint32_t* out_reasons
   if (bt->B == 0 || s->C == 0) return KP_OK;
   // bindings in chunks of at most kChunkPairs pairs through one reused device
   // buffer (a 100k x 5k batch would otherwise take 2 GB on each side)
-  size_t chunk = (size_t)1 << 24;
-  if (const char* v = getenv("KP_REASONS_CHUNK")) chunk = std::max<size_t>(1, (size_t)atoll(v));  // (tests)
+  const size_t chunk = std::max<size_t>(1, (size_t)kp_env_int("KP_REASONS_CHUNK", 1 << 24));  // (tests lower it)
   const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)bt->B, chunk / (size_t)s->C));
   const size_t pairs = (size_t)nb * s->C;
   uint32_t* d = nullptr;

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "kp_dev.h"
+#include "kp_env.h"
 #include "kp_kernels.h"
 #include "kp_sets.h"
 #include "kp_top.h"
@@ -222,16 +223,6 @@ extern "C" __global__ void __launch_bounds__(64 * kTopWaves) k_select_top_list(K
     body_select_top(WaveBlk{(int64_t*)mine}, blk, mine, a, t);
     __builtin_amdgcn_wave_barrier();  // (the next binding re-carves the slice)
   }
-}
-#else
-;
-#endif
-// The large-subset bindings: one workgroup each, wave 0 walks, the workgroup divides.
-extern "C" __global__ void __launch_bounds__(64 * kTopWgWaves) k_select_top_wg(KArgs a, TopArgs t)
-#if KP_K(4)
-{
-  KP_SMEM;
-  body_select_top_wg(GpuBlk{(int64_t*)smem}, WaveBlk{(int64_t*)top_wg_slice(smem)}, (int)blockIdx.x, smem, a, t);
 }
 #else
 ;
@@ -527,13 +518,11 @@ extern "C" __global__ void __launch_bounds__(kOffThreads) k_offsets_b(int n, uin
 extern "C" __global__ void __launch_bounds__(64) k_compact(const uint64_t* start, const uint32_t* count,
                                                            const uint64_t* offsets, const uint32_t* in_idx,
                                                            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep,
-                                                           int n, const uint32_t* perm, uint32_t* h_idx,
-                                                           int32_t* h_rep, uint64_t h_cap)
+                                                           int n, const uint32_t* perm)
 #if KP_K(8)
 {
   __shared__ int64_t red[8];
-  body_compact(GpuBlk{red}, (int)blockIdx.x, start, count, offsets, in_idx, in_rep, out_idx, out_rep, n, perm, h_idx,
-               h_rep, h_cap);
+  body_compact(GpuBlk{red}, (int)blockIdx.x, start, count, offsets, in_idx, in_rep, out_idx, out_rep, n, perm);
 }
 #else
 ;
@@ -576,8 +565,7 @@ thread_local hipError_t g_err = hipSuccess;
 // so wider workgroups add latency hiding). KP_SEL_THREADS overrides for tuning.
 int sel_threads() {
   static int n = [] {
-    const char* e = getenv("KP_SEL_THREADS");
-    int v = e ? atoi(e) : KP_SEL_MAX_THREADS;
+    const int v = (int)kp_env_int("KP_SEL_THREADS", KP_SEL_MAX_THREADS);
     return (v == 128 || v == 256 || v == 512) && v <= KP_SEL_MAX_THREADS ? v : KP_SEL_MAX_THREADS;
   }();
   return n;
@@ -613,10 +601,7 @@ void stream_destroy(stream_t s) { (void)hipStreamDestroy((hipStream_t)s); }
 // KP_SYNC_BLOCK=1: host waits sleep in the driver (hipEventBlockingSync) instead of polling,
 // so lane threads waiting on their batches leave the process's CPU quota to the others
 static bool blocking_sync() {
-  static const bool on = [] {
-    const char* v = getenv("KP_SYNC_BLOCK");
-    return v && atoi(v) != 0;
-  }();
+  static const bool on = kp_env_int("KP_SYNC_BLOCK", 0) != 0;
   return on;
 }
 int sync(stream_t s) {
@@ -644,8 +629,8 @@ float event_ms(event_t a, event_t b) {
 
 int alloc(void** p, size_t bytes) { return chk(hipMalloc(p, bytes)); }
 void release(void* p) { (void)hipFree(p); }
-// (mapped and coherent: the result CSR is written into it by k_compact, uncached, and read
-// by the host after the stream's synchronisation)
+// (page-locked, mapped and coherent: the target of the result copies, read by the host
+// after the stream's synchronisation)
 int host_alloc(void** p, size_t bytes) {
   return chk(hipHostMalloc(p, bytes ? bytes : 1, hipHostMallocMapped | hipHostMallocCoherent));
 }
@@ -741,7 +726,7 @@ int select(stream_t st, int which, const KArgs& a, size_t smem, int cap, const S
       // a device-appended list: a persistent grid of a few workgroups per CU
       int g = a.n_dev ? std::min(a.n, 256 * 4) : a.n;
       if (a.n_dev && x.list_grid > 0) g = std::min(g, x.list_grid);
-      if (smem > kLdsPerCu / 2 && !getenv("KP_SEL_THREADS"))  // one workgroup per CU: go wide
+      if (smem > kLdsPerCu / 2 && !kp_env_flag("KP_SEL_THREADS"))  // one workgroup per CU: go wide
         hipLaunchKernelGGL(k_select_all_wide, dim3(g), dim3(1024), smem, h, a);
       else
         hipLaunchKernelGGL(k_select_all, dim3(g), dim3(sel_threads()), smem, h, a);
@@ -830,15 +815,6 @@ int select_top(stream_t st, const KArgs& a, const TopArgs& t, size_t slice, int 
   return chk(hipGetLastError());
 }
 
-int select_top_wg(stream_t st, const KArgs& a, const TopArgs& t, size_t smem) {
-  if (a.n <= 0) return 0;
-  if (smem > 65536 &&
-      chk(hipFuncSetAttribute((const void*)k_select_top_wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)))
-    return -1;
-  hipLaunchKernelGGL(k_select_top_wg, dim3(a.n), dim3(64 * kTopWgWaves), smem, (hipStream_t)st, a, t);
-  return chk(hipGetLastError());
-}
-
 int spread_order(stream_t st, const KArgs& a, const OrderArgs& o, size_t slice) {
   if (a.n <= 0) return 0;
   const size_t smem = slice * kOrderWaves;
@@ -874,7 +850,7 @@ int region_groups(stream_t st, const RegionOut* rout, const int32_t* rstat, cons
                   int n, int R, int32_t* rsel, int32_t* rnsel, uint32_t* nhost) {
   if (n <= 0) return 0;
   const size_t lds = groups_lds_bytes(R, kGroupsLdsThreads);
-  if (R >= 1 && lds <= 65536 && !getenv("KP_GROUPS_PRIV"))
+  if (R >= 1 && lds <= 65536)
     hipLaunchKernelGGL(k_region_groups_lds, dim3((n + kGroupsLdsThreads - 1) / kGroupsLdsThreads), dim3(kGroupsLdsThreads),
                        lds, (hipStream_t)st, rout, rstat, hdr, list, n, R, rsel, rnsel, nhost);
   else
@@ -956,11 +932,10 @@ int offsets(stream_t st, const int32_t* status, const uint32_t* count, int n, ui
 }
 
 int compact(stream_t st, const uint64_t* start, const uint32_t* count, const uint64_t* offsets, const uint32_t* in_idx,
-            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm, uint32_t* h_idx,
-            int32_t* h_rep, uint64_t h_cap) {
+            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_compact, dim3(n), dim3(64), 0, (hipStream_t)st, start, count, offsets, in_idx, in_rep, out_idx,
-                     out_rep, n, perm, h_idx, h_rep, h_cap);
+                     out_rep, n, perm);
   return chk(hipGetLastError());
 }
 int pack(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint32_t* in_idx, const int32_t* in_rep,
@@ -976,7 +951,6 @@ int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const
   hipLaunchKernelGGL(k_pack_wide, dim3(n), dim3(64), 0, (hipStream_t)st, start, offsets, wide_offsets, in_rep, out, n);
   return chk(hipGetLastError());
 }
-int host_device_ptr(void* host, void** dev) { return chk(hipHostGetDevicePointer(dev, host, 0)); }
 
 }  // namespace dev
 }  // namespace kp

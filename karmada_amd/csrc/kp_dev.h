@@ -96,8 +96,6 @@ int class_order(stream_t st, const SnapView& s, const int32_t* rows, int n_rows,
 // (a.n_dev set: the list's length is on the device, a.n its capacity; max_grid > 0
 // bounds the grid, whose waves then stride over the list)
 int select_top(stream_t st, const KArgs& a, const TopArgs& t, size_t slice, int max_grid = 0);
-// k_select_top_wg: one workgroup per binding (the large-subset bindings), smem = top_wg_lds_bytes
-int select_top_wg(stream_t st, const KArgs& a, const TopArgs& t, size_t smem);
 // selectGroups for n region bindings (one thread each): rsel/rnsel as the host
 // step writes them; *nhost counts the bindings left to the host (kGroupsHost).
 int region_groups(stream_t st, const RegionOut* rout, const int32_t* rstat, const BindHdr* hdr, const int32_t* list,
@@ -144,11 +142,8 @@ int reasons(stream_t st, const SnapView& s, const BatchView& bv, int b0, int nb,
 // part: ceil(n / kOffChunk) u64 of scratch.
 int offsets(stream_t st, const int32_t* status, const uint32_t* count, int n, uint64_t* off, uint64_t* part);
 // (in_idx holds snapshot ranks; out_idx gets perm[rank], the caller's cluster index)
-// h_idx / h_rep (device addresses of page-locked host buffers, h_cap entries each): the
-// CSR entries below h_cap are also written there, over the bus, by the kernel itself.
 int compact(stream_t st, const uint64_t* start, const uint32_t* count, const uint64_t* offsets, const uint32_t* in_idx,
-            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm,
-            uint32_t* h_idx = nullptr, int32_t* h_rep = nullptr, uint64_t h_cap = 0);
+            const int32_t* in_rep, uint32_t* out_idx, int32_t* out_rep, int n, const uint32_t* perm);
 // The packed result form (kp_results_packed), in compact's place: out[offsets[b] + i] = the
 // packed word of binding b's entry i (perm[rank] | replicas << 16, 0xFFFF for escaped
 // replicas) and wide_count[b] = its escaped entries (body_pack); then, with wide_offsets
@@ -158,8 +153,6 @@ int pack(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint
          uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm);
 int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint64_t* wide_offsets,
               const int32_t* in_rep, int32_t* out, int n);
-// The device address of page-locked host memory from host_alloc (the same on the host build).
-int host_device_ptr(void* host, void** dev);
 
 }  // namespace dev
 }  // namespace kp

@@ -92,7 +92,6 @@ constexpr int kSlowBlock = 512;  // k_slow: wider for the LDS bitonic sort
 #define KP_ORDER_WAVES 4
 #endif
 constexpr int kTopWaves = KP_TOP_WAVES;        // k_select_top
-constexpr int kTopWgWaves = 4;                 // k_select_top_wg: one binding per workgroup of this many waves
 constexpr int kStaticWaves = KP_STATIC_WAVES;  // k_select_static
 constexpr int kOrderWaves = KP_ORDER_WAVES;    // k_spread_order, k_region_a_order
 constexpr int kPairStage = 4096;  // bytes of per-binding predicate data staged in LDS

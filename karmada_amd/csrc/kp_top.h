@@ -167,12 +167,6 @@ constexpr int kTopRowRegs = 2;  // feasibility-row words preloaded per lane (C <
 constexpr int kTopStream = 8;  // row chunks per step of the no-class-order passes
 static_assert(kTopAhead % kTopGroup == 0, "the ring holds whole groups");
 
-// Hand-off of a binding from wave 0's walk to its workgroup's selection (k_select_top_wg).
-struct TopHand {
-  int32_t go, n, complete, pad;
-  int64_t F;
-};
-
 // The LDS slice of one binding: [red 64 B | mask W u64 | S votes cap | S ranks cap |
 // SelScratch], carved the same way by every wave that reads it. The mask holds the
 // feasibility row, then (after the scheduled clusters are taken) the feasible clusters
@@ -206,11 +200,8 @@ KP_HD inline int32_t target_rep(const SelCtx& x, uint32_t rank) {
   return 0;
 }
 
-// hand: wave 0 of a k_select_top_wg workgroup stops after the walk and leaves the
-// selection to the whole workgroup (the subset is in the slice, the counts in *hand).
 template <class BLK>
-KP_FI void body_select_top(const BLK& B, int blk, unsigned char* smem, const KArgs& a, const TopArgs& t,
-                           TopHand* hand = nullptr) {
+KP_FI void body_select_top(const BLK& B, int blk, unsigned char* smem, const KArgs& a, const TopArgs& t) {
   if (blk >= a.n) return;
   KP_STAMP_INIT
   const int b = a.list[blk];
@@ -727,10 +718,6 @@ KP_FI void body_select_top(const BLK& B, int blk, unsigned char* smem, const KAr
   KP_COUNT(x, 47 + (agg ? 1 : 0), 1);
   cd.F = n;
   B.sync();
-  if (hand) {
-    if (B.tid() == 0) *hand = TopHand{1, n, complete ? 1 : 0, 0, F};
-    return;
-  }
   const TopInfo ti{F, complete};
   int why;
   if (n <= B.nth()) {  // (wave-uniform) at most one candidate per lane, in registers
@@ -742,38 +729,6 @@ KP_FI void body_select_top(const BLK& B, int blk, unsigned char* smem, const KAr
   KP_STAMP(x, 12);
   if (why == SLOW_TOP_FULL) top_fallback(B, a, t, b);
   else if (why != SLOW_NONE && B.tid() == 0) flag_slow(a, b, why);
-}
-
-// k_select_top_wg: one workgroup of kTopWgWaves waves per binding for the bindings that
-// need a large subset (the second launch): wave 0 runs the walk exactly as the one-wave
-// kernel does, then the whole workgroup runs the division over the subset, whose passes
-// (Webster over hundreds of parties) dominate such a binding. LDS: [GpuBlk red |
-// TopHand 64 B | the one-wave slice].
-KP_HD inline size_t top_wg_lds_bytes(int Cp, int cap) { return kRedBytes + 64 + top_lds_bytes(Cp, cap); }
-// W: wave 0's block policy over the slice (its red area = the slice's first 64 B).
-KP_HD inline unsigned char* top_wg_slice(unsigned char* smem) { return smem + kRedBytes + 64; }
-template <class GBLK, class WBLK>
-KP_FI void body_select_top_wg(const GBLK& G, const WBLK& W, int blk, unsigned char* smem, const KArgs& a,
-                              const TopArgs& t) {
-  if (blk >= a.n) return;  // (block-uniform)
-  TopHand* hand = (TopHand*)(smem + kRedBytes);
-  unsigned char* slice = top_wg_slice(smem);
-  if (G.tid() == 0) hand->go = 0;
-  if (G.wid() == 0) body_select_top(W, blk, slice, a, t, hand);
-  G.sync();
-  const TopHand hh = *hand;
-  if (!hh.go) return;  // wave 0 wrote the result or handed the binding on
-  const int b = a.list[blk];
-  TopCarve tc = top_carve(slice, a.s, t.cap, a.dbg);
-  const BindHdr hloc = a.bv.hdr[b];  // registers: no reload after LDS stores
-  SelCtx x = make_ctx(a, b, (const uint32_t*)tc.frow);  // (wave 0 left the target bits there)
-  x.h = &hloc;
-  x.frow = tc.frow;
-  tc.cd.F = hh.n;
-  const TopInfo ti{hh.F, hh.complete != 0};
-  const int why = sel_all_fast<true>(G, x, TopCands{&tc.cd, G.tid(), G.nth()}, tc.ss, &ti);
-  if (why == SLOW_TOP_FULL) top_fallback(G, a, t, b);
-  else if (why != SLOW_NONE && G.tid() == 0) flag_slow(a, b, why);
 }
 
 }  // namespace kp

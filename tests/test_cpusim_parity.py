@@ -183,14 +183,13 @@ def test_cpusim_top_subsets(top_env):
         e.close()
 
 
-@pytest.mark.parametrize("slow_env", [{"KP_SLOW_ORDER": "1"}, {"KP_SLOW_ORDER": "0"}, {"KP_TOP_WG": "1"}],
-                         ids=["order", "sort", "top-wg"])
-def test_cpusim_slow_order_and_top_wg(slow_env):
+@pytest.mark.parametrize("slow_env", [{"KP_SLOW_ORDER": "1"}, {"KP_SLOW_ORDER": "0"}],
+                         ids=["order", "sort"])
+def test_cpusim_slow_order(slow_env):
     """k_slow's candidate order from the class orders (kp_kernels.h slow_items_from_order:
     the filtered class order, spec.Clusters merged in) against the bitonic sort it replaces,
-    and the workgroup form of k_select_top for the large subsets, on config 7 (Aggregated
-    tie groups straddling the cut: every tie binding goes through k_slow, 20% with
-    spec.Clusters) and config 3: the oracle's placements every way."""
+    on config 7 (Aggregated tie groups straddling the cut: every tie binding goes through
+    k_slow, 20% with spec.Clusters) and config 3: the oracle's placements either way."""
     old = {k: os.environ.get(k) for k in slow_env}
     os.environ.update(slow_env)
     try:
