@@ -445,7 +445,10 @@ void kp_engine_destroy(kp_engine* e);
 const char* kp_last_error(const kp_engine* e);
 
 /* Packs a cluster list (cache.Snapshot) into the device SoA layout and uploads it.
- * Replaces the per-Schedule List+DeepCopy (cache.go:124-139) by one upload. */
+ * Replaces the per-Schedule List+DeepCopy (cache.go:124-139) by one upload.
+ * KP_ENOTSUP above 2^18 = 262 144 clusters: that is the bound of the encoding (the rank
+ * field of the sort key), not of the engine. A snapshot is usable only up to what
+ * kp_batch_create accepts over it, see there: about 18.6k clusters on gfx950. */
 int kp_snapshot_create(kp_engine* e, const kp_cluster* clusters, uint64_t n_clusters,
                        const kp_options* opts, kp_snapshot** out);
 void kp_snapshot_destroy(kp_snapshot* s);
@@ -466,7 +469,15 @@ int kp_snapshot_update(kp_engine* e, kp_snapshot* s, const kp_cluster* clusters,
 int kp_snapshot_export(const kp_snapshot* s, const void** bytes, uint64_t* n_bytes);
 int kp_snapshot_import(kp_engine* e, const void* bytes, uint64_t n_bytes, kp_snapshot** out);
 
-/* Packs a batch of bindings against a snapshot and uploads them to HBM. */
+/* Packs a batch of bindings against a snapshot and uploads them to HBM.
+ * KP_ENOTSUP ("snapshot too large for one workgroup's LDS") when a selection kernel's
+ * working set over the snapshot does not fit one workgroup's LDS; the schedule calls
+ * check again (a kp_snapshot_update can change the region and template counts). The
+ * kernels gather 8 B per cluster, 10 B in the region-spread stages, beside 12-19 KB of
+ * fixed lists, so with gfx950's 163 840 B per workgroup the ceiling is 18 624 clusters
+ * (about 18.6k) for a batch without spread bindings and 14 336 (about 14.3k) for one
+ * with cluster or region spread bindings (at 16 regions; every further region takes 12 B).
+ * The cluster count rounds up to 64, so the next accepted step is 64 clusters lower. */
 int kp_batch_create(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
                     uint64_t n_bindings, kp_batch** out);
 void kp_batch_destroy(kp_batch* b);
@@ -611,7 +622,8 @@ int kp_schedule_batch_collect(kp_engine* e, kp_batch* b, kp_results* out);
  * kp_engine_set_profile). A submitted call is collected by its own format's function:
  * the other one returns KP_ESTATE and leaves the call collectable. A batch may be
  * scheduled in either format from call to call. KP_ENOTSUP for a snapshot of more than
- * 65 536 clusters. */
+ * 65 536 clusters (the bound of the 16-bit index field; kp_batch_create's LDS ceiling is
+ * lower, so no batch reaches it). */
 int kp_schedule_batch_packed(kp_engine* e, kp_batch* b, kp_results_packed* out);
 int kp_schedule_batch_submit_packed(kp_engine* e, kp_batch* b);
 int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* b, kp_results_packed* out);

@@ -9,6 +9,8 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -20,6 +22,8 @@
 
 namespace kp {
 namespace dev {
+
+size_t max_lds_per_block(int) { return 160 * 1024; }
 
 namespace {
 int threads() {
@@ -34,29 +38,76 @@ bool poison() {
   static const bool on = kp_env_int("KP_CPUSIM_POISON", 1) != 0;
   return on;
 }
-// Runs fn(blk, smem) for blk in [0, n) on the configured host threads.
+// A workgroup's LDS is exactly the bytes its launch asked for (kp_launch.h's size
+// functions, the same the HIP launch takes), then a guard band. An LDS access past the
+// allocation raises nothing on the device: a store is dropped and a load gives zero, so a
+// carve that outgrows its size function shows, if at all, as a wrong placement. Here the
+// band holds a fixed pattern (not the poison's), checked after every workgroup; a
+// damaged band, or a launch that asks more than max_lds_per_block(), fails the launch
+// with the kernel's name in last_error(). Always on: the CPU suite is the check.
+constexpr size_t kGuardBytes = 4096;
+constexpr unsigned char kGuardByte = 0x5C;
+thread_local std::string g_err = "cpusim error";
+// KP_CPUSIM_LDS_SHRINK=<n> (test hook): every launch gets n bytes less than it asked
+// for, as if its launcher had under-asked by n (tests/test_lds_ceiling.py).
+size_t lds_shrink() {
+  const long long n = kp_env_int("KP_CPUSIM_LDS_SHRINK", 0);
+  return n > 0 ? (size_t)n : 0;
+}
+// Runs fn(blk, smem) for blk in [0, n) on the configured host threads; kernel names the
+// launch in its errors. Returns -1 (and sets last_error()) when the launch is refused or
+// a workgroup wrote past its LDS; the workgroups not yet started are then skipped.
 template <class F>
-void grid(int n, size_t smem_bytes, F fn) {
+int grid(const char* kernel, int n, size_t smem_bytes, F fn) {
+  if (smem_bytes > max_lds_per_block(0)) {
+    g_err = std::string(kernel) + ": the launch asks " + std::to_string(smem_bytes) + " bytes of LDS, a workgroup has " +
+            std::to_string(max_lds_per_block(0));
+    return -1;
+  }
+  if (n <= 0) return 0;
+  const size_t shrink = lds_shrink();
+  smem_bytes = smem_bytes > shrink ? smem_bytes - shrink : 0;
   int T = threads();
   if (T > n) T = n;
   std::atomic<int> next(0);
+  std::atomic<bool> bad(false);
+  std::mutex mu;
+  std::string err;
   const bool pz = poison();
   auto work = [&]() {
-    std::vector<int64_t> smem((smem_bytes + kRedBytes + 7) / 8);
+    // (16-byte aligned as the device's dynamic LDS; the band starts at the first byte
+    // past the request, whatever its alignment)
+    std::vector<unsigned char> mem(smem_bytes + kGuardBytes + 16);
+    unsigned char* sm = mem.data() + ((16 - ((uintptr_t)mem.data() & 15)) & 15);
+    unsigned char* band = sm + smem_bytes;
+    memset(band, kGuardByte, kGuardBytes);
     for (;;) {
       int b = next.fetch_add(1);
-      if (b >= n) break;
-      if (pz) memset(smem.data(), 0xA5, smem.size() * 8);
-      fn(b, (unsigned char*)smem.data());
+      if (b >= n || bad.load()) break;
+      if (pz) memset(sm, 0xA5, smem_bytes);
+      fn(b, sm);
+      for (size_t i = 0; i < kGuardBytes; i++)
+        if (band[i] != kGuardByte) {
+          std::lock_guard<std::mutex> lk(mu);
+          if (!bad.exchange(true))
+            err = std::string(kernel) + ": workgroup " + std::to_string(b) + " wrote past its " +
+                  std::to_string(smem_bytes) + " bytes of LDS (guard band damaged at offset " + std::to_string(i) + ")";
+          return;
+        }
     }
   };
   if (T <= 1) {
     work();
-    return;
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; t++) th.emplace_back(work);
+    for (auto& t : th) t.join();
   }
-  std::vector<std::thread> th;
-  for (int t = 0; t < T; t++) th.emplace_back(work);
-  for (auto& t : th) t.join();
+  if (bad.load()) {
+    g_err = err;
+    return -1;
+  }
+  return 0;
 }
 struct Ev {
   double ms;
@@ -69,8 +120,7 @@ int device_count() {
   return n < 1 ? 1 : n;
 }
 int set_device(int) { return 0; }
-size_t max_lds_per_block(int) { return 160 * 1024; }
-const char* last_error() { return "cpusim error"; }
+const char* last_error() { return g_err.c_str(); }
 int stream_create(stream_t* s) {
   *s = (void*)1;
   return 0;
@@ -118,7 +168,7 @@ int fill(void* dst, int value, size_t bytes, stream_t) {
 
 int pair(stream_t, const SnapView& s, const BatchView& bv, const int32_t* list, int b0, int nb, uint64_t* fmask,
          int32_t* est, int64_t* score, int est_mode, int md_cap, size_t smem, int fast) {
-  grid(nb, smem, [&](int blk, unsigned char* sm) {
+  return grid("k_pair", nb, smem, [&](int blk, unsigned char* sm) {
     const CpuBlk B{(int64_t*)sm};
     switch (fast) {
       case EST_MIXED: body_pair<EST_MIXED>(B, blk, sm, s, bv, list, b0, fmask, est, score, est_mode, md_cap); break;
@@ -128,12 +178,15 @@ int pair(stream_t, const SnapView& s, const BatchView& bv, const int32_t* list, 
       default: body_pair<EST_GENERIC>(B, blk, sm, s, bv, list, b0, fmask, est, score, est_mode, md_cap);
     }
   });
-  return 0;
 }
 
 int est_class(stream_t, const SnapView& s, const BatchView& bv, const int32_t* rep, int n_rows, int32_t* rows,
               int fast, const int32_t* klist, const uint64_t* fmask) {
-  grid(n_rows, 4 * kTmplDense + (fmask ? 4 * (size_t)s.Cp : 0), [&](int i, unsigned char* sm) {
+  if (fast != EST_MIXED && fast != EST_SUMMARY && fast != EST_MODEL8 && fast != EST_MODEL16) {
+    g_err = "k_est_class: no instance for this estimator kind";
+    return -1;
+  }
+  return grid("k_est_class", n_rows, est_class_lds_bytes(s.Cp, fmask != nullptr), [&](int i, unsigned char* sm) {
     const CpuBlk B{(int64_t*)sm};
     const int k = klist ? klist[i] : i;
     switch (fast) {
@@ -144,59 +197,46 @@ int est_class(stream_t, const SnapView& s, const BatchView& bv, const int32_t* r
       default: break;
     }
   });
-  return fast == EST_MIXED || fast == EST_SUMMARY || fast == EST_MODEL8 || fast == EST_MODEL16 ? 0 : -1;
 }
 
 int filter(stream_t, const SnapView& s, const BatchView& bv, uint64_t* fmask) {
-  grid(bv.B, 0, [&](int b, unsigned char* sm) { body_filter(CpuBlk{(int64_t*)sm}, b, s, bv, fmask); });
-  return 0;
+  return grid("k_filter", bv.B, 0, [&](int b, unsigned char* sm) { body_filter(CpuBlk{(int64_t*)sm}, b, s, bv, fmask); });
 }
 
 int filter_extra(stream_t, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, uint64_t* fmask,
                  int32_t* est) {
-  grid(n, 0, [&](int i, unsigned char* sm) {
+  return grid("k_filter_extra", n, 0, [&](int i, unsigned char* sm) {
     body_filter_extra(CpuBlk{(int64_t*)sm}, i, s.C, s.Cp, s.W, list, rows, fmask, est);
   });
-  return 0;
 }
 
 int reasons_extra(stream_t, const SnapView& s, const FltPair* list, int n, const uint64_t* rows, int b0,
                   uint32_t* out) {
-  grid(n, 0, [&](int i, unsigned char* sm) {
+  return grid("k_reasons_extra", n, 0, [&](int i, unsigned char* sm) {
     body_reasons_extra(CpuBlk{(int64_t*)sm}, i, s.C, s.W, list, rows, b0, out);
   });
-  return 0;
 }
 
 int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const SelectExtra& x) {
   switch (which) {
-    case SEL_LAUNCH_ALL: {
-      const int n = a.n_dev ? (int)*a.n_dev : a.n;
-      const size_t need = kRedBytes + 4 * (size_t)((((a.s.Cp + 31) >> 5) + 3) & ~3) + 8 * (size_t)a.s.Cp + 3072 +
-                          8 * (size_t)sel_all_ecap(a.s.Cp) + 64;
-      grid(n, need > smem ? need : smem,
-           [&](int blk, unsigned char* sm) { body_select_all(CpuBlk{(int64_t*)sm}, blk, sm, a); });
-      break;
-    }
+    case SEL_LAUNCH_ALL:
+      return grid("k_select_all", a.n_dev ? (int)*a.n_dev : a.n, smem,
+                  [&](int blk, unsigned char* sm) { body_select_all(CpuBlk{(int64_t*)sm}, blk, sm, a); });
     case SEL_LAUNCH_ALL_STREAM:
-      grid(a.n_dev ? (int)*a.n_dev : a.n, smem,
-           [&](int blk, unsigned char* sm) { body_select_all_stream(CpuBlk{(int64_t*)sm}, blk, sm, a); });
-      break;
+      return grid("k_select_all_stream", a.n_dev ? (int)*a.n_dev : a.n, smem,
+                  [&](int blk, unsigned char* sm) { body_select_all_stream(CpuBlk{(int64_t*)sm}, blk, sm, a); });
     case SEL_LAUNCH_CLUSTER:
-      grid(a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
+      return grid("k_select_cluster", a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
         body_select_cluster(CpuBlk{(int64_t*)sm}, a.sub ? a.sub[j] : j, sm, a, cap);
       });
-      break;
     case SEL_LAUNCH_REGION_A:
-      grid(a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
+      return grid("k_region_a", a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
         body_region_a(CpuBlk{(int64_t*)sm}, a.sub ? a.sub[j] : j, sm, a, x.rout, x.rstat);
       });
-      break;
     case SEL_LAUNCH_REGION_B:
-      grid(a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
+      return grid("k_region_b", a.n_dev ? (int)*a.n_dev : a.n, smem, [&](int j, unsigned char* sm) {
         body_region_b(CpuBlk{(int64_t*)sm}, a.sub ? a.sub[j] : j, sm, a, x.rsel, x.rnsel, x.rout, cap);
       });
-      break;
     case SEL_LAUNCH_SLOW: {
       // On the GPU the flagged list's order is the order of the device atomics that
       // appended it, so which bindings follow each other in one workgroup's slot
@@ -211,40 +251,39 @@ int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const Sele
         }
       }
       const int g = std::max(1, std::min(x.grid, (int)kp_env_int("KP_CPUSIM_SLOW_GRID", x.grid)));
-      grid(g, smem, [&](int blk, unsigned char* sm) {
+      return grid("k_slow", g, smem, [&](int blk, unsigned char* sm) {
         body_slow(CpuBlk{(int64_t*)sm}, blk, g, sm, a, x.scratch, x.slot_bytes, cap, x.lds_area, x.lds_sort);
       });
-      break;
     }
     default:
+      g_err = "select: unknown launch";
       return -1;
   }
-  return 0;
 }
 
 int region_wide(stream_t, const KArgs& a, const SelectExtra& x, const int32_t* wide, int n_wide,
                 unsigned char* scratch, size_t slot_bytes, int g, int cap, int lds_sort, uint32_t* n_done) {
   if (n_wide <= 0 || g <= 0) return 0;
-  grid(g, region_wide_lds_bytes(a.s.Cp, a.s.n_regions, lds_sort), [&](int blk, unsigned char* sm) {
-    body_region_wide(CpuBlk{(int64_t*)sm}, blk, g, sm, a, wide, n_wide, x.rsel, x.rnsel, scratch, slot_bytes, cap,
-                     lds_sort, n_done);
-  });
-  return 0;
+  return grid("k_region_wide", g, region_wide_lds_bytes(a.s.Cp, a.s.n_regions, lds_sort),
+              [&](int blk, unsigned char* sm) {
+                body_region_wide(CpuBlk{(int64_t*)sm}, blk, g, sm, a, wide, n_wide, x.rsel, x.rnsel, scratch,
+                                 slot_bytes, cap, lds_sort, n_done);
+              });
 }
 
 int class_order(stream_t, const SnapView& s, const int32_t* rows, int n_rows, uint64_t* ord, int64_t* tot,
                 int32_t* ok) {
-  int P = 1;
-  while (P < s.C) P <<= 1;
-  grid(n_rows, 8 * (size_t)P, [&](int k, unsigned char* sm) {
+  if (n_rows <= 0 || s.C <= 0) return 0;
+  const int P = class_order_pad(s.C);
+  return grid("k_class_order", n_rows, class_order_lds_bytes(P), [&](int k, unsigned char* sm) {
     body_class_order(CpuBlk{(int64_t*)sm}, k, (uint64_t*)(sm + kRedBytes), P, s, rows, ord, tot, ok);
   });
-  return 0;
 }
 
 int select_top(stream_t, const KArgs& a, const TopArgs& t, size_t slice, int) {
-  grid(a.n_dev ? (int)*a.n_dev : a.n, slice, [&](int blk, unsigned char* sm) { body_select_top(CpuBlk{(int64_t*)sm}, blk, sm, a, t); });
-  return 0;
+  // (one wave per "workgroup" here: the slice of one of the device workgroup's kTopWaves waves)
+  return grid("k_select_top", a.n_dev ? (int)*a.n_dev : a.n, slice,
+              [&](int blk, unsigned char* sm) { body_select_top(CpuBlk{(int64_t*)sm}, blk, sm, a, t); });
 }
 
 int region_groups(stream_t, const RegionOut* rout, const int32_t* rstat, const BindHdr* hdr, const int32_t* list,
@@ -271,18 +310,16 @@ int sets_rows(stream_t, const SnapView& s, const SetsArgs* A, const int64_t* off
 
 int rows_from_class(stream_t, const SnapView& s, const BatchView& bv, const int32_t* list, int n, const int32_t* bcls,
                     const int32_t* cls_rows, const uint64_t* fmask, int32_t* est) {
-  grid(n, 0, [&](int blk, unsigned char* sm) {
+  return grid("k_rows_from_class", n, 0, [&](int blk, unsigned char* sm) {
     body_rows_from_class(CpuBlk{(int64_t*)sm}, blk, s, bv, list, bcls, cls_rows, fmask, est);
   });
-  return 0;
 }
 
 int est_extra(stream_t, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
               const int32_t* extra, int32_t* rows) {
-  grid(n, 0, [&](int blk, unsigned char* sm) {
+  return grid("k_est_extra", n, 0, [&](int blk, unsigned char* sm) {
     body_est_extra(CpuBlk{(int64_t*)sm}, blk, 0, 1, Cp, list, bcls, cls_est, extra, rows);
   });
-  return 0;
 }
 
 int grades(stream_t, const GradesArgs& A) {
@@ -298,21 +335,20 @@ int node_est(stream_t, const NodeEstArgs& A) {
 }
 
 int spread_order(stream_t, const KArgs& a, const OrderArgs& o, size_t slice) {
-  grid(a.n, slice, [&](int blk, unsigned char* sm) { body_spread_order(CpuBlk{(int64_t*)sm}, blk, sm, a, o); });
-  return 0;
+  return grid("k_spread_order", a.n, slice,
+              [&](int blk, unsigned char* sm) { body_spread_order(CpuBlk{(int64_t*)sm}, blk, sm, a, o); });
 }
 
 int region_a_order(stream_t, const KArgs& a, RegionOut* rout, int32_t* rstat, int32_t* fb, uint32_t* fb_n,
                    size_t slice) {
-  grid(a.n, slice, [&](int blk, unsigned char* sm) {
+  return grid("k_region_a_order", a.n, slice, [&](int blk, unsigned char* sm) {
     body_region_a_order(CpuBlk{(int64_t*)sm}, blk, sm, a, rout, rstat, fb, fb_n);
   });
-  return 0;
 }
 
 int select_static(stream_t, const KArgs& a, size_t slice) {
-  grid(a.n, slice, [&](int blk, unsigned char* sm) { body_select_static(CpuBlk{(int64_t*)sm}, blk, sm, a); });
-  return 0;
+  return grid("k_select_static", a.n, slice,
+              [&](int blk, unsigned char* sm) { body_select_static(CpuBlk{(int64_t*)sm}, blk, sm, a); });
 }
 
 int node_match(stream_t, const NodeView& v, const ClaimProg* P, int K, uint8_t* match) {

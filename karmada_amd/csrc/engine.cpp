@@ -1889,31 +1889,12 @@ void parallel_for(int n, int threads, F fn) {
   for (auto& t : th) t.join();
 }
 
-size_t smem_pair(const kp_snapshot* s, int md_cap) {
-  int words = (s->Cp + 31) >> 5;
-  return kRedBytes + 8 * (size_t)words + 4 * (size_t)((md_cap + 3) & ~3) + kPairStage + kTsetMax / 8 + 64;
-}
-size_t smem_all(const kp_snapshot* s) {
-  int words = (s->Cp + 31) >> 5;
-  return kRedBytes + 4 * (size_t)((words + 3) & ~3) + 8 * (size_t)s->Cp + 3072 + 8 * (size_t)sel_all_ecap(s->Cp) + 64;
-}
-size_t smem_cluster(const kp_snapshot* s, int cap) {
-  int words = (s->Cp + 31) >> 5;
-  size_t area = std::max(8 * (size_t)s->Cp, serial_scratch_bytes(cap));
-  return kRedBytes + 1024 + sizeof(Item) * 2 * kSmallMax + 16 * kSmallMax + 4 * (size_t)((words + 3) & ~3) + area + 64;
-}
-size_t smem_region_a(const kp_snapshot* s) {
-  int words = (s->Cp + 31) >> 5;
-  size_t R = s->view.n_regions;
-  return kRedBytes + 80 * R + 4 * (size_t)((words + 3) & ~3) + 10 * (size_t)s->Cp + 64;
-}
-size_t smem_region_b(const kp_snapshot* s, int cap) {
-  int words = (s->Cp + 31) >> 5;
-  size_t R = s->view.n_regions;
-  size_t area = std::max(10 * (size_t)s->Cp, serial_scratch_bytes(cap));  // cand r/v/g, then the serial scratch
-  return kRedBytes + 1024 + sizeof(Item) * 2 * kSmallMax + 16 * kSmallMax + 8 * R + 4 * ((R + 3) & ~3) +
-         4 * (size_t)((words + 3) & ~3) + area + 64;
-}
+// The kernels' dynamic LDS for snapshot s (kp_launch.h: the sizes every launcher takes).
+size_t smem_pair(const kp_snapshot* s, int md_cap) { return pair_lds_bytes(s->Cp, md_cap); }
+size_t smem_all(const kp_snapshot* s) { return sel_all_lds_bytes(s->Cp); }
+size_t smem_cluster(const kp_snapshot* s, int cap) { return sel_cluster_lds_bytes(s->Cp, cap); }
+size_t smem_region_a(const kp_snapshot* s) { return region_a_lds_bytes(s->Cp, s->view.n_regions); }
+size_t smem_region_b(const kp_snapshot* s, int cap) { return region_b_lds_bytes(s->Cp, s->view.n_regions, cap); }
 const int kMdCap = 4096;
 // MaxDivided table entries staged per workgroup: the snapshot's template count.
 int md_cap_of(const kp_snapshot* s) { return s->n_tmpl <= kMdCap ? std::max(kTmplDense, s->n_tmpl) : 0; }
@@ -3324,7 +3305,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   int P = 1;
   while (P < s->Cp) P <<= 1;
   {  // LDS for the candidate sorts (bitonic keys, then the sort.Sort emulation)
-    const size_t base = kRedBytes + 512 + 4 * (size_t)(((s->Cp + 31) >> 5) + 4) + bt->slow_lds;
+    const size_t base = slow_lds_bytes(s->Cp, bt->slow_lds, 0);
     const size_t sel = 3072 + 8 * (size_t)sel_all_ecap(s->Cp) + 64;  // SelScratch of the tie route
     const size_t pdq = (std::max(pdq_wave_bytes(s->Cp), sel) + 15) & ~(size_t)15;
     const size_t both = std::max(8 * (size_t)P, pdq);
@@ -3413,7 +3394,8 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     a.add(&bt->d_fb, std::max(1, bt->n_all_dyn));
     a.add(&bt->d_ofb, std::max(1, bt->n_all_dyn));
   }
-  const bool with_orders = s->C <= 16384 && !bt->crep.empty() && orders_pay && kRedBytes + 8 * (size_t)P <= e->max_lds;
+  const bool with_orders = s->C <= 16384 && !bt->crep.empty() && orders_pay &&
+                           class_order_lds_bytes(class_order_pad(s->C)) <= e->max_lds;
   // singleton classes: feasible entries only, when every reader gathers feasible candidates
   // (no class orders, which sort whole rows; no spread lists; no component-set classes)
   static const bool est_single_on = kp_env_int("KP_EST_SINGLE", 1) != 0;
@@ -4228,7 +4210,7 @@ static int submit_slow(SubmitCtx& c) {
     sxs.grid = (int)std::min<uint32_t>((uint32_t)bt->slow_grid, nslow);
     KPROF(s3, "k_slow", 0, 0,
           dev::select(s3, SEL_LAUNCH_SLOW, k,
-                      kRedBytes + 512 + 4 * (size_t)(((s->Cp + 31) >> 5) + 4) + c.sx.lds_area + c.sx.lds_sort,
+                      slow_lds_bytes(s->Cp, c.sx.lds_area, c.sx.lds_sort),
                       bt->slow_cap, sxs));
   }
   HIPCHK(dev::event_record(e->ev[9], s3));

@@ -679,7 +679,7 @@ int est_class(stream_t st, const SnapView& s, const BatchView& bv, const int32_t
                                   : nullptr;
   if (!k) return chk(hipErrorInvalidValue);
   // (the feasible mode compacts the representative's feasible clusters into LDS)
-  const size_t smem = kRedBytes + 4 * kTmplDense + (fmask ? 4 * (size_t)s.Cp : 0);
+  const size_t smem = est_class_lds_bytes(s.Cp, fmask != nullptr);
   if (smem > 65536 &&
       chk(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)))
     return -1;
@@ -785,9 +785,8 @@ int region_wide(stream_t st, const KArgs& a, const SelectExtra& x, const int32_t
 int class_order(stream_t st, const SnapView& s, const int32_t* rows, int n_rows, uint64_t* ord, int64_t* tot,
                 int32_t* ok) {
   if (n_rows <= 0 || s.C <= 0) return 0;
-  int P = 1;
-  while (P < s.C) P <<= 1;
-  const size_t smem = kRedBytes + 8 * (size_t)P;
+  const int P = class_order_pad(s.C);
+  const size_t smem = class_order_lds_bytes(P);
   if (smem > 65536 &&
       chk(hipFuncSetAttribute((const void*)k_class_order, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)))
     return -1;

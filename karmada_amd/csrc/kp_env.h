@@ -39,6 +39,7 @@
 //   KP_CPUSIM_POISON         1         process  test     CPU build: 0 leaves a workgroup's LDS unpoisoned
 //   KP_CPUSIM_SLOW_SHUFFLE   unset     call     test     CPU build: seed that permutes k_slow's flagged list
 //   KP_CPUSIM_SLOW_GRID      (grid)    call     test     CPU build: upper bound of k_slow's grid
+//   KP_CPUSIM_LDS_SHRINK     0         call     test     CPU build: bytes taken off every launch's LDS request (the guard band's test)
 #pragma once
 
 #include <cstdlib>

@@ -106,4 +106,55 @@ KP_HD inline size_t sel_stream_lds_bytes(int Cp) {
   return kRedBytes + 4 * (size_t)((words + 3) & ~3) + 8 * (size_t)kSwRules * W + 3072 + 8 * (size_t)sel_all_ecap(Cp) +
          64;
 }
+// Dynamic LDS of the other kernels that carve it by cluster count: the one size both device
+// builds launch with (kernels.hip; dev_cpu.cpp, whose workgroups get exactly these bytes and
+// a guard band behind them) and batch_lds_check holds against the device's limit. Each
+// follows its body's carve in kp_kernels.h: [red | ...], 8 B per cluster of gathered
+// candidates (rank, votes) and 2 B more of region ids in the region stages.
+// k_pair* (pair_lds_carve): target and eviction bits, MaxDivided table, predicate stage, taint bits.
+KP_HD inline size_t pair_lds_bytes(int Cp, int md_cap) {
+  const int words = (Cp + 31) >> 5;
+  return kRedBytes + 8 * (size_t)words + 4 * (size_t)((md_cap + 3) & ~3) + kPairStage + kTsetMax / 8 + 64;
+}
+// k_select_all / _wide (body_select_all): target bits, candidates, SelScratch.
+KP_HD inline size_t sel_all_lds_bytes(int Cp) {
+  const int words = (Cp + 31) >> 5;
+  return kRedBytes + 4 * (size_t)((words + 3) & ~3) + 8 * (size_t)Cp + 3072 + 8 * (size_t)sel_all_ecap(Cp) + 64;
+}
+// k_select_cluster (body_select_cluster): cap = entries of its serial scratch.
+KP_HD inline size_t sel_cluster_lds_bytes(int Cp, int cap) {
+  const int words = (Cp + 31) >> 5;
+  const size_t cand = 8 * (size_t)Cp, ser = serial_scratch_bytes(cap);
+  return kRedBytes + 1024 + sizeof(Item) * 2 * kSmallMax + 16 * kSmallMax + 4 * (size_t)((words + 3) & ~3) +
+         (cand > ser ? cand : ser) + 64;
+}
+// k_region_a (body_region_a), R regions.
+KP_HD inline size_t region_a_lds_bytes(int Cp, int R) {
+  const int words = (Cp + 31) >> 5;
+  return kRedBytes + 80 * (size_t)R + 4 * (size_t)((words + 3) & ~3) + 10 * (size_t)Cp + 64;
+}
+// k_region_b (body_region_b): cand r/v/g, then the serial scratch in their place.
+KP_HD inline size_t region_b_lds_bytes(int Cp, int R, int cap) {
+  const int words = (Cp + 31) >> 5;
+  const size_t cand = 10 * (size_t)Cp, ser = serial_scratch_bytes(cap);
+  return kRedBytes + 1024 + sizeof(Item) * 2 * kSmallMax + 16 * kSmallMax + 8 * (size_t)R + 4 * (size_t)((R + 3) & ~3) +
+         4 * (size_t)((words + 3) & ~3) + (cand > ser ? cand : ser) + 64;
+}
+// k_est_class* (body_est_class): the MaxDivided table; feasible: and the representative's
+// feasible clusters compacted behind it (at most Cp).
+KP_HD inline size_t est_class_lds_bytes(int Cp, bool feasible) {
+  return kRedBytes + 4 * (size_t)kTmplDense + (feasible ? 4 * (size_t)Cp : 0);
+}
+// k_class_order (body_class_order): the bitonic sort's P = class_order_pad(C) keys.
+KP_HD inline int class_order_pad(int C) {
+  int P = 1;
+  while (P < C) P <<= 1;
+  return P;
+}
+KP_HD inline size_t class_order_lds_bytes(int P) { return kRedBytes + 8 * (size_t)P; }
+// k_slow (body_slow): target bits, lds_area bytes for the small serial problems, lds_sort
+// for the candidate sorts.
+KP_HD inline size_t slow_lds_bytes(int Cp, int lds_area, int lds_sort) {
+  return kRedBytes + 512 + 4 * (size_t)(((Cp + 31) >> 5) + 4) + (size_t)lds_area + (size_t)lds_sort;
+}
 }  // namespace kp
