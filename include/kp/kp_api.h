@@ -671,6 +671,44 @@ enum {
 };
 int kp_filter_reasons(kp_engine* e, kp_batch* b, uint32_t* out_reasons);
 
+/* FitError diagnosis of a batch's failed bindings at batch cost: FitError.Error()
+ * (framework/types.go:73-89) never looks at pairs, it counts clusters per distinct reason
+ * string, so this call returns that histogram per binding instead of kp_filter_reasons'
+ * n_bindings*n_clusters words. A bin is one distinct reason string of the reference:
+ * KP_REASON_API and KP_REASON_AFFINITY .. KP_REASON_OUT_OF_TREE are one bin each;
+ * KP_REASON_TAINT is one bin per distinct taint text, i.e. per (key, value, effect) of the
+ * cluster's first untolerated NoSchedule/NoExecute taint (the taint kp_filter_reasons'
+ * argument indexes). Within a binding the bins are ordered by reason code, then taint_ref;
+ * empty bins are absent. Per binding n_fit + n_deleting + the sum of its counts = n_clusters.
+ *
+ * taint_ref names a taint the caller can print: a caller cluster index in bits [17:0] and
+ * above them the index of the taint among that cluster's NoSchedule/NoExecute taints (the
+ * encoding of kp_filter_reasons' argument). The cluster is the snapshot-wide representative
+ * of the triple, the lowest caller cluster index that carries it (with its first position
+ * there), fixed when the snapshot is created, updated or imported; it need not be a cluster
+ * this binding rejected.
+ *
+ * bindings != NULL: exactly those n batch indices, strictly ascending and below the batch
+ * size (KP_EINVAL otherwise). bindings == NULL (n ignored): the bindings whose status was
+ * KP_STATUS_FIT_ERROR in the batch's last completed schedule call, plain or packed, one
+ * call or submit + collect; KP_ESTATE when there is none, or while a submitted call is not
+ * collected. The arrays belong to the engine and stay valid until the next call on it.
+ * enabled_plugins and a kp_batch_create_filters batch's rows are honoured as by
+ * kp_filter_reasons, and like it the call is not refused for n_out_of_tree_plugins > 0. */
+typedef struct kp_fit_diagnosis {
+  uint64_t n_bindings;          /* bindings diagnosed */
+  const uint64_t* binding;      /* n_bindings: index in the batch, ascending */
+  const uint64_t* offsets;      /* n_bindings + 1: CSR into the three arrays below */
+  const uint32_t* reason;       /* KP_REASON_* (1..8; never FIT or DELETING) */
+  const uint32_t* taint_ref;    /* KP_REASON_TAINT: (caller cluster index) | (taint index << 18); else 0 */
+  const uint32_t* count;        /* clusters in this bin, > 0 */
+  const uint32_t* n_fit;        /* n_bindings: clusters that pass every filter */
+  const uint32_t* n_deleting;   /* n_bindings: clusters skipped as deleting */
+  uint64_t n_bins;
+} kp_fit_diagnosis;
+int kp_fit_diagnosis_batch(kp_engine* e, kp_batch* b, const uint64_t* bindings /* may be NULL */, uint64_t n,
+                           kp_fit_diagnosis* out);
+
 /* ScorePlugin boundary: summed score (RunScorePlugins) per pair; n_bindings*n_clusters. */
 int kp_score_batch(kp_engine* e, kp_batch* b, int64_t* out_scores);
 

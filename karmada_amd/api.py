@@ -173,6 +173,17 @@ class kp_results(C.Structure):
                 ("cluster_idx", C.POINTER(u32)), ("replicas", C.POINTER(i32)), ("n_targets", u64)]
 
 
+class kp_fit_diagnosis(C.Structure):
+    """kp_fit_diagnosis_batch: per diagnosed binding the FitError reason histogram as CSR
+    bins (reason code, taint_ref, cluster count) plus its fitting and deleting clusters."""
+    _fields_ = [("n_bindings", u64), ("binding", C.POINTER(u64)), ("offsets", C.POINTER(u64)),
+                ("reason", C.POINTER(u32)), ("taint_ref", C.POINTER(u32)), ("count", C.POINTER(u32)),
+                ("n_fit", C.POINTER(u32)), ("n_deleting", C.POINTER(u32)), ("n_bins", u64)]
+
+
+TAINT_REF_CLUSTER_BITS = 18  # taint_ref = caller cluster index | taint index << 18
+
+
 class kp_results_packed(C.Structure):
     """kp_results in 4 bytes per target: targets[i] = cluster index | replicas << 16, the
     replicas 0xFFFF when outside 0..65534 and then the next entry of wide_replicas
@@ -341,8 +352,18 @@ def fit_error_message(num_all_clusters: int, reasons: dict) -> str:
     for rs in reasons.values():
         for r in ([rs] if isinstance(rs, str) else rs):
             hist[r] = hist.get(r, 0) + 1
+    return fit_error_histogram_message(num_all_clusters, hist)
+
+
+def fit_error_histogram_message(num_all_clusters: int, hist: dict) -> str:
+    """FitError.Error() from the reason histogram itself, {reason text: cluster count}
+    (types.go:73-89 builds exactly this map before it sorts and joins)."""
+    if num_all_clusters == 0 or not hist:
+        return "0/%d clusters are available: %s." % (num_all_clusters, "no cluster exists")
     return "0/%d clusters are available: %s." % (num_all_clusters,
                                                    ", ".join(sorted("%d %s" % (v, k) for k, v in hist.items())))
+
+
 ERR_NAMES = {
     0: "none", 1: "fit", 2: "region_min_groups", 3: "region_cluster_min", 4: "cluster_min_groups",
     5: "cluster_resource", 6: "spread_unsupported", 7: "no_clusters", 8: "unsupported_strategy",

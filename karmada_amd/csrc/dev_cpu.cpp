@@ -369,6 +369,27 @@ int reasons(stream_t, const SnapView& s, const BatchView& bv, int b0, int nb, ui
   return 0;
 }
 
+// (one "wave" per workgroup here, so each gets exactly one wave's fit_hist_lds_bytes())
+int fit_hist(stream_t, const SnapView& s, const BatchView& bv, const int32_t* list, const int32_t* frow, int n,
+             const uint64_t* flt_rows, uint32_t* dense) {
+  if (s.W <= 0) return 0;
+  return grid("k_fit_hist", n, fit_hist_lds_bytes(), [&](int i, unsigned char* sm) {
+    body_fit_hist(CpuBlk{nullptr}, i, (int32_t*)sm, s, bv, list, frow, flt_rows, dense);
+  });
+}
+int reason_hist(stream_t, const SnapView& s, const uint32_t* words, int n, uint32_t* dense) {
+  return grid("k_reason_hist", n, 0, [&](int i, unsigned char*) { body_reason_hist(CpuBlk{nullptr}, i, s, words, dense); });
+}
+int hist_count(stream_t, int n, int U, const uint32_t* dense, uint32_t* nbins) {
+  return grid("k_hist_count", n, 0, [&](int i, unsigned char*) { body_hist_count(CpuBlk{nullptr}, i, U, dense, nbins); });
+}
+int hist_write(stream_t, int n, int U, const uint32_t* uid_ref, const uint32_t* dense, const uint64_t* offsets,
+               uint32_t* reason, uint32_t* taint_ref, uint32_t* count, uint32_t* n_fit, uint32_t* n_del) {
+  return grid("k_hist_write", n, 0, [&](int i, unsigned char*) {
+    body_hist_write(CpuBlk{nullptr}, i, U, uid_ref, dense, offsets, reason, taint_ref, count, n_fit, n_del);
+  });
+}
+
 int offsets(stream_t, const int32_t* status, const uint32_t* count, int n, uint64_t* off, uint64_t* part) {
   int64_t red[8];
   const int nb = (n + kOffChunk - 1) / kOffChunk;

@@ -298,6 +298,10 @@ struct kp_engine {
     std::vector<uint32_t> cidx;
     std::vector<int32_t> rep;
   } aff;
+  struct {  // kp_fit_diagnosis_batch results
+    std::vector<uint64_t> binding, offsets;
+    std::vector<uint32_t> reason, taint_ref, count, n_fit, n_del;
+  } diag;
   int n_threads = 8;
   size_t max_lds = 65536;
   // k_select_top (kp_top.h): on, and its subset capacity per binding (LDS entries);
@@ -482,6 +486,7 @@ struct kp_batch {
   int32_t* h_crep = nullptr;
   uint64_t h_res_cap = 0;
   SchedPend pend;         // a submitted call (schedule_submit) awaiting schedule_finish
+  bool sched_done = false;  // h_status holds a completed schedule call's statuses (kp_fit_diagnosis_batch)
   size_t h_cidx_bytes = 0, h_crep_bytes = 0;  // their pooled block sizes
   // The packed result form (kp_results_packed), allocated on the batch's first packed call
   // (ensure_packed): per-binding escape counts [B] and their scan [B + 1] on the device,
@@ -880,6 +885,27 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
     if (trep.empty()) trep.push_back(0);
   }
   int32_t *d_tset, *d_trep, *d_mt = nullptr;
+  // FitError diagnosis: one id per distinct (key, value, effect) triple, i.e. per distinct
+  // taint text, and the taint_ref that names it: the lowest caller cluster index that carries
+  // the triple with its first position there. Ids are numbered in taint_ref order, so a
+  // binding's taint bins come out of the dense histogram rows already sorted.
+  std::vector<int32_t> tuid(s->taint_key.size(), 0);
+  std::vector<uint32_t> uref;
+  if (!tuid.empty()) {
+    std::map<std::array<int32_t, 3>, uint32_t> ref_of;
+    auto triple = [&](int t) { return std::array<int32_t, 3>{s->taint_key[t], s->taint_val[t], s->taint_eff[t]}; };
+    for (int i = 0; i < C; i++) {
+      const int r = s->inv[i];
+      for (int t = s->taint_off[r]; t < s->taint_off[r + 1]; t++)
+        ref_of.emplace(triple(t), (uint32_t)i | (uint32_t)(t - s->taint_off[r]) << kTaintRefShift);
+    }
+    for (auto& kv : ref_of) uref.push_back(kv.second);
+    std::sort(uref.begin(), uref.end());
+    for (size_t t = 0; t < tuid.size(); t++)
+      tuid[t] = (int32_t)(std::lower_bound(uref.begin(), uref.end(), ref_of[triple((int)t)]) - uref.begin());
+  }
+  int32_t* d_tuid = nullptr;
+  uint32_t* d_uref = nullptr;
   // Cluster bitsets of the filter predicates (kp_filter.h; SnapView::bits).
   std::vector<uint64_t> bits, bkey;
   std::vector<int32_t> bval;
@@ -977,6 +1003,10 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
   a.add(&d_tk, s->taint_key.size());
   a.add(&d_tv, s->taint_val.size());
   a.add(&d_te, s->taint_eff.size());
+  if (!tuid.empty()) {
+    a.add(&d_tuid, tuid.size());
+    a.add(&d_uref, uref.size());
+  }
   a.add(&d_mtid, s->mg_tid.size());
   a.add(&d_mcnt, s->mg_cnt.size());
   a.add(&d_pint, Cp);
@@ -1010,6 +1040,10 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
   HIPCHK(up(d_tk, s->taint_key.data(), 4 * s->taint_key.size()));
   HIPCHK(up(d_tv, s->taint_val.data(), 4 * s->taint_val.size()));
   HIPCHK(up(d_te, s->taint_eff.data(), 4 * s->taint_eff.size()));
+  if (!tuid.empty()) {
+    HIPCHK(up(d_tuid, tuid.data(), 4 * tuid.size()));
+    HIPCHK(up(d_uref, uref.data(), 4 * uref.size()));
+  }
   HIPCHK(up(d_mtid, s->mg_tid.data(), 4 * s->mg_tid.size()));
   HIPCHK(up(d_mcnt, s->mg_cnt.data(), 4 * s->mg_cnt.size()));
   HIPCHK(up(d_pint, s->provider_int.data(), 8 * Cp));
@@ -1042,6 +1076,9 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
   v.taint_set = d_tset;
   v.tset_rep = d_trep;
   v.n_tsets = (int32_t)trep.size();
+  v.taint_uid = d_tuid;
+  v.uid_ref = d_uref;
+  v.n_taint_uid = (int32_t)uref.size();
   v.api_bits = d_api;
   v.allowed = d_allowed;
   v.avail = d_avail;
@@ -2443,6 +2480,7 @@ int kp_snapshot_replicate(kp_engine* e, const kp_snapshot* src, kp_snapshot** ou
   rb(v.zone_off), rb(v.zone_ids), rb(v.label_val), rb(v.taint_off), rb(v.taint_key), rb(v.taint_val);
   rb(v.taint_eff), rb(v.taint_set), rb(v.tset_rep), rb(v.api_bits), rb(v.allowed), rb(v.avail), rb(v.qa);
   rb(v.mg_tid), rb(v.mg_cnt), rb(v.tmpl), rb(v.mt_cnt), rb(v.bits), rb(v.bkey), rb(v.bval);
+  rb(v.taint_uid), rb(v.uid_ref);
   s->est_kind = src->est_kind;
   *out = guard.release();
   return KP_OK;
@@ -4279,6 +4317,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
     pd = SchedPend{};
     pd.ev = ev;
   }
+  bt->sched_done = false;
   pd.packed = packed;
   pd.t0 = now_ms();
   pd.seq = ++e->submit_seq;
@@ -4347,6 +4386,8 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   const int B = bt->B;
   if (pd.empty) {
     bt->h_offsets.assign(1, 0);
+    bt->h_status.clear();
+    bt->sched_done = true;
     if (packed) {
       memset(pout, 0, sizeof(*pout));
       pout->offsets = bt->h_offsets.data();
@@ -4488,6 +4529,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   tm.copy_ms = t1 - tc0;
   tm.total_ms = t1 - t0;
   e->times = tm;
+  bt->sched_done = true;
   if (packed) {
     pout->n_bindings = (uint64_t)B;
     pout->status = bt->h_status.data();
@@ -4647,6 +4689,152 @@ static int filter_reasons_impl(kp_engine* e, kp_batch* bt, uint32_t* out_reasons
   return KP_OK;
 }
 int kp_filter_reasons(kp_engine* e, kp_batch* bt, uint32_t* out_reasons) { return batch_fence(e, bt, filter_reasons_impl(e, bt, out_reasons)); }
+
+// One chunk of kp_fit_diagnosis_batch: the dense histogram rows of the bindings list[i0, i0 + m)
+// (k_fit_hist over the snapshot's bitset rows; without them k_reasons / k_reasons_extra over
+// each run of consecutive bindings, then k_reason_hist), compacted into the CSR on the device
+// (count, k_offsets_a/b, write) and appended to the engine's result arrays. Only the chunk's
+// offsets, its bins and n_fit / n_deleting are copied back.
+struct DiagBufs {
+  int32_t *list, *frow, *status0;
+  uint32_t *dense, *words, *nbins, *n_fit, *n_del;
+  uint64_t *off, *part;
+};
+static int fit_diagnosis_chunk(kp_engine* e, kp_batch* bt, const std::vector<int32_t>& list, const DiagBufs& d,
+                               bool bits, int i0, int m) {
+  kp_snapshot* s = bt->snap;
+  const SnapView& v = s->view;
+  const int U = v.n_taint_uid, S = hist_stride(U);
+  auto& D = e->diag;
+  dev::stream_t st = e->stream;
+  HIPCHK(dev::fill(d.dense, 0, 4 * (size_t)m * S, st));
+  if (bits) {
+    HIPCHK(dev::fit_hist(st, v, bt->view, d.list + i0, d.frow + i0, m, bt->d_flt_rows, d.dense));
+  } else {
+    auto below = [](const FltPair& p, int b) { return p.b < b; };
+    for (int j = 0; j < m;) {  // runs of consecutive binding indices: one k_reasons launch each
+      int k = j + 1;
+      while (k < m && list[i0 + k] == list[i0 + k - 1] + 1) k++;
+      const int b0 = list[i0 + j], nb = k - j;
+      uint32_t* w = d.words + (size_t)j * s->C;
+      const size_t f0 = std::lower_bound(bt->l_flt.begin(), bt->l_flt.end(), b0, below) - bt->l_flt.begin();
+      const size_t f1 = std::lower_bound(bt->l_flt.begin(), bt->l_flt.end(), b0 + nb, below) - bt->l_flt.begin();
+      HIPCHK(dev::reasons(st, v, bt->view, b0, nb, w));
+      HIPCHK(dev::reasons_extra(st, v, bt->d_flt_list + f0, (int)(f1 - f0), bt->d_flt_rows, b0, w));
+      j = k;
+    }
+    HIPCHK(dev::reason_hist(st, v, d.words, m, d.dense));
+  }
+  HIPCHK(dev::hist_count(st, m, U, d.dense, d.nbins));
+  HIPCHK(dev::offsets(st, d.status0, d.nbins, m, d.off, d.part));
+  std::vector<uint64_t> off((size_t)m + 1);
+  HIPCHK(dev::d2h(off.data(), d.off, 8 * off.size(), st));
+  HIPCHK(dev::sync(st));  // (the chunk's bin total sizes the CSR arrays)
+  const uint64_t tot = off[m], base = D.reason.size();
+  Arena csr;
+  uint32_t *reason, *tref, *count;
+  csr.add(&reason, tot);
+  csr.add(&tref, tot);
+  csr.add(&count, tot);
+  HIPCHK(csr.alloc());
+  HIPCHK(dev::hist_write(st, m, U, v.uid_ref, d.dense, d.off, reason, tref, count, d.n_fit, d.n_del));
+  D.reason.resize(base + tot);
+  D.taint_ref.resize(base + tot);
+  D.count.resize(base + tot);
+  int rc = dev::d2h(D.reason.data() + base, reason, 4 * tot, st) || dev::d2h(D.taint_ref.data() + base, tref, 4 * tot, st) ||
+           dev::d2h(D.count.data() + base, count, 4 * tot, st) ||
+           dev::d2h(D.n_fit.data() + i0, d.n_fit, 4 * (size_t)m, st) ||
+           dev::d2h(D.n_del.data() + i0, d.n_del, 4 * (size_t)m, st);
+  rc = dev::sync(st) || rc;  // (csr is released below: nothing may still write it)
+  if (rc) {
+    e->err = std::string("kp_fit_diagnosis_batch: ") + dev::last_error();
+    return KP_EDEVICE;
+  }
+  for (int j = 0; j < m; j++) D.offsets[(size_t)i0 + j + 1] = base + off[(size_t)j + 1];
+  return KP_OK;
+}
+
+static int fit_diagnosis_impl(kp_engine* e, kp_batch* bt, const uint64_t* bindings, uint64_t n, kp_fit_diagnosis* out) {
+  if (!e || !bt || !out) return KP_EINVAL;
+  (void)dev::set_device(e->device);
+  kp_snapshot* s = bt->snap;
+  std::vector<int32_t> list;
+  if (bindings) {
+    for (uint64_t i = 0; i < n; i++) {
+      if (bindings[i] >= (uint64_t)bt->B || (i > 0 && bindings[i] <= bindings[i - 1])) {
+        e->err = "kp_fit_diagnosis_batch: the binding indices must be strictly ascending and below the batch size";
+        return KP_EINVAL;
+      }
+      list.push_back((int32_t)bindings[i]);
+    }
+  } else {
+    if (bt->pend.live || !bt->sched_done) {
+      e->err = bt->pend.live ? "kp_fit_diagnosis_batch: the batch's submitted call is not collected"
+                             : "kp_fit_diagnosis_batch: the batch has no completed schedule call";
+      return KP_ESTATE;
+    }
+    for (int b = 0; b < (int)bt->h_status.size(); b++)
+      if (bt->h_status[b] == KP_STATUS_FIT_ERROR) list.push_back(b);
+  }
+  const int N = (int)list.size();
+  auto& D = e->diag;
+  D.binding.assign(list.begin(), list.end());
+  D.offsets.assign((size_t)N + 1, 0);
+  D.reason.clear();
+  D.taint_ref.clear();
+  D.count.clear();
+  D.n_fit.assign((size_t)N + 1, 0);  // (+ 1: data() of an empty list is still an array)
+  D.n_del.assign((size_t)N + 1, 0);
+  int rc = KP_OK;
+  if (N > 0) {
+    const bool bits = s->view.n_bits > 0 && !kp_env_flag("KP_PAIR_ROWS");
+    std::vector<int32_t> frow((size_t)N, -1);  // the listed bindings' rows of out-of-tree verdicts
+    for (size_t i = 0, f = 0; i < frow.size() && f < bt->l_flt.size(); i++) {
+      while (f < bt->l_flt.size() && bt->l_flt[f].b < list[i]) f++;
+      if (f < bt->l_flt.size() && bt->l_flt[f].b == list[i]) frow[i] = bt->l_flt[f].r;
+    }
+    // bindings per chunk: the dense rows, and without the bitset rows the reason words, of
+    // one chunk stay within KP_REASONS_CHUNK words each (kp_filter_reasons' buffer bound)
+    const size_t S = (size_t)hist_stride(s->view.n_taint_uid);
+    const size_t chunk = std::max<size_t>(1, (size_t)kp_env_int("KP_REASONS_CHUNK", 1 << 24));
+    const size_t per = bits ? S : std::max(S, (size_t)s->C);
+    const int nbc = (int)std::max<size_t>(1, std::min<size_t>((size_t)N, chunk / per));
+    Arena a;
+    DiagBufs d{};
+    a.add(&d.list, (size_t)N);
+    a.add(&d.frow, (size_t)N);
+    a.add(&d.status0, (size_t)nbc);
+    a.add(&d.dense, (size_t)nbc * S);
+    a.add(&d.words, bits ? 0 : (size_t)nbc * s->C);
+    a.add(&d.nbins, (size_t)nbc);
+    a.add(&d.n_fit, (size_t)nbc);
+    a.add(&d.n_del, (size_t)nbc);
+    a.add(&d.off, (size_t)nbc + 1);
+    a.add(&d.part, (size_t)(nbc + kOffChunk - 1) / kOffChunk);
+    HIPCHK(a.alloc());
+    rc = dev::h2d(d.list, list.data(), 4 * (size_t)N, e->stream) || dev::h2d(d.frow, frow.data(), 4 * (size_t)N, e->stream) ||
+                 dev::fill(d.status0, 0, 4 * (size_t)nbc, e->stream)  // (KP_STATUS_OK: k_offsets_a counts every row)
+             ? KP_EDEVICE
+             : KP_OK;
+    if (rc) e->err = std::string("kp_fit_diagnosis_batch: ") + dev::last_error();
+    for (int i0 = 0; i0 < N && rc == KP_OK; i0 += nbc) rc = fit_diagnosis_chunk(e, bt, list, d, bits, i0, std::min(nbc, N - i0));
+    if (rc) (void)dev::sync(e->stream);  // (the arena is released here: nothing may still use it)
+  }
+  if (rc) return rc;
+  out->n_bindings = (uint64_t)N;
+  out->binding = D.binding.data();
+  out->offsets = D.offsets.data();
+  out->reason = D.reason.data();
+  out->taint_ref = D.taint_ref.data();
+  out->count = D.count.data();
+  out->n_fit = D.n_fit.data();
+  out->n_deleting = D.n_del.data();
+  out->n_bins = (uint64_t)D.reason.size();
+  return KP_OK;
+}
+int kp_fit_diagnosis_batch(kp_engine* e, kp_batch* bt, const uint64_t* bindings, uint64_t n, kp_fit_diagnosis* out) {
+  return batch_fence(e, bt, fit_diagnosis_impl(e, bt, bindings, n, out));
+}
 
 }  // extern "C"
 

@@ -496,6 +496,62 @@ extern "C" __global__ void __launch_bounds__(256) k_reasons(SnapView s, BatchVie
 #else
 ;
 #endif
+// kp_fit_diagnosis_batch: one wave64 per listed binding, kFitHistWaves per workgroup, the item
+// index through a scalar register as k_filter. k_fit_hist: the reason histogram by bitset
+// algebra (each wave its fit_hist_lds_bytes() of LDS); k_reason_hist: the same dense rows
+// from k_reasons' words; k_hist_count / k_hist_write: the dense rows into the CSR.
+extern "C" __global__ void __launch_bounds__(64 * kFitHistWaves) k_fit_hist(SnapView s, BatchView bv, int n,
+                                                                          const int32_t* list, const int32_t* frow,
+                                                                          const uint64_t* flt_rows, uint32_t* dense)
+#if KP_K(8)
+{
+  KP_SMEM;
+  const int wv = kp_uniform((int)(threadIdx.x >> 6));
+  const int i = (int)(blockIdx.x * kFitHistWaves) + wv;
+  if (i >= n) return;  // wave-uniform
+  body_fit_hist(WaveBlk{nullptr}, i, (int32_t*)(smem + (size_t)wv * fit_hist_lds_bytes()), s, bv, list, frow, flt_rows,
+                dense);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kFitHistWaves) k_reason_hist(SnapView s, int n,
+                                                                             const uint32_t* words,
+                                                                             uint32_t* dense)
+#if KP_K(8)
+{
+  const int i = (int)(blockIdx.x * kFitHistWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n) return;  // wave-uniform
+  body_reason_hist(WaveBlk{nullptr}, i, s, words, dense);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kFitHistWaves) k_hist_count(int n, int U, const uint32_t* dense,
+                                                                            uint32_t* nbins)
+#if KP_K(8)
+{
+  const int i = (int)(blockIdx.x * kFitHistWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n) return;  // wave-uniform
+  body_hist_count(WaveBlk{nullptr}, i, U, dense, nbins);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kFitHistWaves) k_hist_write(int n, int U, const uint32_t* uid_ref,
+                                                                            const uint32_t* dense,
+                                                                            const uint64_t* offsets, uint32_t* reason,
+                                                                            uint32_t* taint_ref, uint32_t* count,
+                                                                            uint32_t* n_fit, uint32_t* n_del)
+#if KP_K(8)
+{
+  const int i = (int)(blockIdx.x * kFitHistWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n) return;  // wave-uniform
+  body_hist_write(WaveBlk{nullptr}, i, U, uid_ref, dense, offsets, reason, taint_ref, count, n_fit, n_del);
+}
+#else
+;
+#endif
 extern "C" __global__ void __launch_bounds__(kOffThreads) k_offsets_a(const int32_t* status, const uint32_t* count, int n,
                                                                     uint64_t* offsets, uint64_t* part)
 #if KP_K(8)
@@ -919,6 +975,32 @@ int reasons(stream_t st, const SnapView& s, const BatchView& bv, int b0, int nb,
   if (n == 0) return 0;
   const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, 8192);
   hipLaunchKernelGGL(k_reasons, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, s, bv, b0, n, out);
+  return chk(hipGetLastError());
+}
+
+static dim3 hist_grid(int n) { return dim3((n + kFitHistWaves - 1) / kFitHistWaves); }
+int fit_hist(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* list, const int32_t* frow, int n,
+             const uint64_t* flt_rows, uint32_t* dense) {
+  if (n <= 0 || s.W <= 0) return 0;
+  hipLaunchKernelGGL(k_fit_hist, hist_grid(n), dim3(64 * kFitHistWaves), kFitHistWaves * fit_hist_lds_bytes(),
+                     (hipStream_t)st, s, bv, n, list, frow, flt_rows, dense);
+  return chk(hipGetLastError());
+}
+int reason_hist(stream_t st, const SnapView& s, const uint32_t* words, int n, uint32_t* dense) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_reason_hist, hist_grid(n), dim3(64 * kFitHistWaves), 0, (hipStream_t)st, s, n, words, dense);
+  return chk(hipGetLastError());
+}
+int hist_count(stream_t st, int n, int U, const uint32_t* dense, uint32_t* nbins) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_hist_count, hist_grid(n), dim3(64 * kFitHistWaves), 0, (hipStream_t)st, n, U, dense, nbins);
+  return chk(hipGetLastError());
+}
+int hist_write(stream_t st, int n, int U, const uint32_t* uid_ref, const uint32_t* dense, const uint64_t* offsets,
+               uint32_t* reason, uint32_t* taint_ref, uint32_t* count, uint32_t* n_fit, uint32_t* n_del) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_hist_write, hist_grid(n), dim3(64 * kFitHistWaves), 0, (hipStream_t)st, n, U, uid_ref, dense,
+                     offsets, reason, taint_ref, count, n_fit, n_del);
   return chk(hipGetLastError());
 }
 

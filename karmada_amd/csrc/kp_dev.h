@@ -138,6 +138,17 @@ int node_match(stream_t st, const NodeView& v, const ClaimProg* P, int K, uint8_
 int node_sets(stream_t st, const NodeSetsArgs* A);
 // kp_filter_reasons: out[(b - b0) * C + r] = pair_reason of binding b in [b0, b0 + nb), cluster rank r.
 int reasons(stream_t st, const SnapView& s, const BatchView& bv, int b0, int nb, uint32_t* out);
+// kp_fit_diagnosis_batch. fit_hist: the dense reason histogram rows dense[i][hist_stride]
+// (zeroed by the caller) of the n bindings list[i] by bitset algebra (body_fit_hist; requires
+// s.n_bits > 0), frow[i] the binding's row of flt_rows or -1. reason_hist: the same rows from
+// n rows of reason words words[i][C] (body_reason_hist). hist_count: nbins[i] = the row's
+// non-zero bins; hist_write: the bins at offsets[i] .. and n_fit / n_del (body_hist_write).
+int fit_hist(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* list, const int32_t* frow, int n,
+             const uint64_t* flt_rows, uint32_t* dense);
+int reason_hist(stream_t st, const SnapView& s, const uint32_t* words, int n, uint32_t* dense);
+int hist_count(stream_t st, int n, int U, const uint32_t* dense, uint32_t* nbins);
+int hist_write(stream_t st, int n, int U, const uint32_t* uid_ref, const uint32_t* dense, const uint64_t* offsets,
+               uint32_t* reason, uint32_t* taint_ref, uint32_t* count, uint32_t* n_fit, uint32_t* n_del);
 // CSR offsets[n + 1] of the per-binding results (counts of OK bindings), on the device;
 // part: ceil(n / kOffChunk) u64 of scratch.
 int offsets(stream_t st, const int32_t* status, const uint32_t* count, int n, uint64_t* off, uint64_t* part);

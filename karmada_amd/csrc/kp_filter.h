@@ -114,30 +114,48 @@ KP_HD inline uint64_t prog_word(const SnapView& s, const BatchView& bv, int32_t 
   return m;
 }
 
+// Word w of the sets a binding's filter stages are made of; filter_word ANDs the stages
+// together, body_fit_hist counts what each one drops.
+// spec.Clusters members, which pass APIEnablement and TaintToleration (TargetContains)
+KP_HD inline uint64_t fw_targets(const BatchView& bv, const BindHdr& h, int w) {
+  return h.tgt_cnt > 0 ? rank_word(bv.ipool + h.tgt_off, h.tgt_cnt, w, 2) : 0ull;
+}
+// clusters that enable the binding's GVK
+KP_HD inline uint64_t fw_api(const SnapView& s, const BindHdr& h, int w) {
+  return h.gvk >= 0 ? bits_word(s, s.br_api + h.gvk, w) : 0ull;
+}
+// clusters whose taint list the binding tolerates (tolm: bit t = it tolerates list t)
+KP_HD inline uint64_t fw_tolerated(const SnapView& s, uint64_t tolm, int w) {
+  uint64_t tl = 0;
+  for (uint64_t t = tolm; t; t &= t - 1) tl |= bits_word(s, s.br_tset + ctz64(t), w);
+  return tl;
+}
+// ClusterAffinity: any term matches
+KP_HD inline uint64_t fw_affinity(const SnapView& s, const BatchView& bv, const BindHdr& h, int w) {
+  uint64_t a = 0;
+  for (int j = 0; j < h.filt_cnt; j++) a |= prog_word(s, bv, kp_ldu(bv.ipool + h.filt_off + j), w);
+  return a;
+}
+// clusters the binding is being evicted from (only with h.evict_cnt > 0)
+KP_HD inline uint64_t fw_evicting(const BatchView& bv, const BindHdr& h, int w) {
+  return rank_word(bv.ipool + h.evict_off, h.evict_cnt, w);
+}
+
 // Feasibility word w of binding h: the same expression as pair_eval_fast's `ok`
 // (kp_algo.h), over bitset rows. tolm: bit t = the binding tolerates taint list t.
 KP_HD inline uint64_t filter_word(const SnapView& s, const BatchView& bv, const BindHdr& h, int w, uint64_t tolm) {
   const int en = h.enabled;
   uint64_t m = bits_word(s, BR_BASE, w);
-  // spec.Clusters members pass APIEnablement and TaintToleration (TargetContains)
-  const uint64_t in_t = h.tgt_cnt > 0 ? rank_word(bv.ipool + h.tgt_off, h.tgt_cnt, w, 2) : 0ull;
-  if (en & 1) m &= in_t | (h.gvk >= 0 ? bits_word(s, s.br_api + h.gvk, w) : 0ull);
-  if (en & 2) {
-    uint64_t tl = 0;
-    for (uint64_t t = tolm; t; t &= t - 1) tl |= bits_word(s, s.br_tset + ctz64(t), w);
-    m &= in_t | tl;
-  }
-  if ((en & 4) && !(h.flags & BF_AFF_ALL)) {  // ClusterAffinity: any term matches
-    uint64_t a = 0;
-    for (int j = 0; j < h.filt_cnt; j++) a |= prog_word(s, bv, kp_ldu(bv.ipool + h.filt_off + j), w);
-    m &= a;
-  }
+  const uint64_t in_t = fw_targets(bv, h, w);
+  if (en & 1) m &= in_t | fw_api(s, h, w);
+  if (en & 2) m &= in_t | fw_tolerated(s, tolm, w);
+  if ((en & 4) && !(h.flags & BF_AFF_ALL)) m &= fw_affinity(s, bv, h, w);
   if (en & 8) {  // SpreadConstraint presence checks
     if (h.flags & BF_NEED_PROVIDER) m &= bits_word(s, BR_HAS_PROVIDER, w);
     if (h.flags & BF_NEED_REGION) m &= bits_word(s, BR_HAS_REGION, w);
     if (h.flags & BF_NEED_ZONES) m &= bits_word(s, BR_HAS_ZONES, w);
   }
-  if ((en & 32) && h.evict_cnt > 0) m &= ~rank_word(bv.ipool + h.evict_off, h.evict_cnt, w);  // ClusterEviction
+  if ((en & 32) && h.evict_cnt > 0) m &= ~fw_evicting(bv, h, w);  // ClusterEviction
   return m;
 }
 
@@ -191,6 +209,146 @@ KP_UNROLL
   for (int w0 = 0; w0 < s.W; w0 += ww) {
     const int w = w0 + lane;
     if (w < s.W) row[w] = filter_word(s, bv, h, w, tolm);
+  }
+}
+
+// FindMatchingUntoleratedTaint over taints [t0, t1): the position of the first one the
+// binding does not tolerate, -1 when it tolerates them all (taints_tolerated_regs' walk,
+// which only needs to know whether there is one).
+KP_FI int first_untolerated_regs(const SnapView& s, const BatchView& bv, const BindHdr& h, const Tol (&tr)[kTolRegs],
+                                 int t0, int t1) {
+  for (int t = t0; t < t1; t++) {
+    const int32_t k = s.taint_key[t], v = s.taint_val[t], e = s.taint_eff[t];
+    auto hit = [&](const Tol& tl) {
+      return (tl.eff == EFF_ANY || tl.eff == e) && (tl.key < 0 || tl.key == k) && (tl.op == TOL_EXISTS || tl.val == v);
+    };
+    bool tol = false;
+KP_UNROLL
+    for (int j = 0; j < kTolRegs; j++) tol = tol | (j < h.tol_cnt && hit(tr[j]));
+    for (int j = kTolRegs; j < h.tol_cnt && !tol; j++) tol = hit(kp_ldu(bv.tols + h.tol_off + j));
+    if (!tol) return t;
+  }
+  return -1;
+}
+
+// k_fit_hist: the FitError reason histogram of binding list[i] (kp_fit_diagnosis_batch),
+// by the calling wave, into its dense row dense[i][hist_stride] (kp_launch.h; zeroed before
+// the launch). A cluster's reason is the first stage of pair_reason's plugin order whose
+// word drops it, so each stage counts popcount(alive & ~stage word) over the words
+// filter_word ANDs together: one lane per word as body_filter, the per-lane counts summed
+// across the wave once at the end. i is wave-uniform, so the list entry, the header and the
+// predicate walk are scalar loads.
+// TaintToleration has one bin per distinct (key, value, effect) triple: the list's first
+// untolerated taint, answered once per distinct taint list (one lane per list, where
+// body_filter computes tolm), names the bin through taint_uid; uidl (kTsetRowsMax words of
+// the wave's LDS) hands each list's bin to the whole wave. A list's rejected clusters are
+// those still alive before the stage, outside spec.Clusters, that hold the list. Several
+// lists may share a bin, so lane 0 adds each list's wave sum to the row with an atomic.
+// frow[i] >= 0: the binding's row of the out-of-tree verdicts flt_rows[..][W], the last stage.
+template <class BLK>
+KP_FI void body_fit_hist(const BLK& B, int i, int32_t* uidl, const SnapView& s, const BatchView& bv,
+                         const int32_t* list, const int32_t* frow, const uint64_t* flt_rows, uint32_t* dense) {
+  const int b = kp_ldu(list + i), fr = kp_ldu(frow + i);
+  const BindHdr h = kp_ldu(bv.hdr + b);
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  const int en = h.enabled, U = s.n_taint_uid;
+  uint32_t* row = dense + (size_t)i * hist_stride(U);
+  uint64_t tolm = 0;
+  if (en & 2) {
+    Tol tr[kTolRegs];
+KP_UNROLL
+    for (int j = 0; j < kTolRegs; j++)
+      tr[j] = j < h.tol_cnt ? kp_ldu(bv.tols + h.tol_off + j) : Tol{0, 0, TOL_EQUAL, -1};
+    for (int t0 = 0; t0 < s.n_tsets; t0 += ww) {
+      const int t = t0 + lane;
+      int fu = -1;
+      if (t < s.n_tsets) {
+        const int c = s.tset_rep[t];
+        fu = first_untolerated_regs(s, bv, h, tr, s.taint_off[c], s.taint_off[c + 1]);
+        uidl[t] = fu >= 0 ? s.taint_uid[fu] : -1;
+      }
+      tolm |= B.wballot(t < s.n_tsets && fu < 0) << t0;
+    }
+    B.wsync();
+  }
+  // alive before TaintToleration (and the spec.Clusters members, which it passes)
+  auto before_taint = [&](int w, uint64_t* in_t) {
+    *in_t = fw_targets(bv, h, w);
+    uint64_t m = bits_word(s, BR_BASE, w);
+    if (en & 1) m &= *in_t | fw_api(s, h, w);
+    return m;
+  };
+  uint32_t n_fit = 0, n_del = 0, c_api = 0, c_aff = 0, c_prov = 0, c_reg = 0, c_zone = 0, c_evict = 0, c_oot = 0;
+  for (int w = lane; w < s.W; w += ww) {
+    const int nv = s.C - 64 * w;  // clusters of this word (the last one's padding bits are no clusters)
+    const uint64_t valid = nv >= 64 ? ~0ull : nv > 0 ? (1ull << nv) - 1 : 0ull;
+    const uint64_t base = bits_word(s, BR_BASE, w);
+    n_del += (uint32_t)popc64(valid & ~base);
+    uint64_t in_t;
+    uint64_t m = before_taint(w, &in_t);
+    c_api += (uint32_t)popc64(base & ~m);
+    if (en & 2) m &= in_t | fw_tolerated(s, tolm, w);  // (counted per list below)
+    if ((en & 4) && !(h.flags & BF_AFF_ALL)) {
+      const uint64_t a = fw_affinity(s, bv, h, w);
+      c_aff += (uint32_t)popc64(m & ~a);
+      m &= a;
+    }
+    if (en & 8) {  // SpreadConstraint: the constraints in spec order
+      for (int k = 0; k < 3; k++) {
+        const int fld = (h.spread_order >> (2 * k)) & 3;
+        if (fld == 0) continue;
+        const uint64_t p = bits_word(s, fld == 1 ? BR_HAS_PROVIDER : fld == 2 ? BR_HAS_REGION : BR_HAS_ZONES, w);
+        const uint32_t d = (uint32_t)popc64(m & ~p);
+        c_prov += fld == 1 ? d : 0u;
+        c_reg += fld == 2 ? d : 0u;
+        c_zone += fld == 3 ? d : 0u;
+        m &= p;
+      }
+    }
+    if ((en & 32) && h.evict_cnt > 0) {
+      const uint64_t ev = fw_evicting(bv, h, w);
+      c_evict += (uint32_t)popc64(m & ev);
+      m &= ~ev;
+    }
+    if (fr >= 0) {
+      const uint64_t x = flt_rows[(size_t)fr * s.W + w];
+      c_oot += (uint32_t)popc64(m & ~x);
+      m &= x;
+    }
+    n_fit += (uint32_t)popc64(m);
+  }
+  if (en & 2) {
+    for (int t = 0; t < s.n_tsets; t++) {
+      if ((tolm >> t) & 1) continue;  // wave-uniform
+      uint32_t c = 0;
+      for (int w = lane; w < s.W; w += ww) {
+        uint64_t in_t;
+        const uint64_t m = before_taint(w, &in_t);
+        c += (uint32_t)popc64(m & ~in_t & bits_word(s, s.br_tset + t, w));
+      }
+      c = (uint32_t)B.wsum32((int32_t)c);
+      if (lane == 0 && c) kp_atomic_add(row + hist_slot_uid(uidl[t]), c);
+    }
+  }
+  n_fit = (uint32_t)B.wsum32((int32_t)n_fit);
+  n_del = (uint32_t)B.wsum32((int32_t)n_del);
+  c_api = (uint32_t)B.wsum32((int32_t)c_api);
+  c_aff = (uint32_t)B.wsum32((int32_t)c_aff);
+  c_prov = (uint32_t)B.wsum32((int32_t)c_prov);
+  c_reg = (uint32_t)B.wsum32((int32_t)c_reg);
+  c_zone = (uint32_t)B.wsum32((int32_t)c_zone);
+  c_evict = (uint32_t)B.wsum32((int32_t)c_evict);
+  c_oot = (uint32_t)B.wsum32((int32_t)c_oot);
+  if (lane == 0) {
+    row[0] = n_fit;
+    row[1] = n_del;
+    row[hist_slot(1, U)] = c_api;
+    row[hist_slot(3, U)] = c_aff;
+    row[hist_slot(4, U)] = c_prov;
+    row[hist_slot(5, U)] = c_reg;
+    row[hist_slot(6, U)] = c_zone;
+    row[hist_slot(7, U)] = c_evict;
+    row[hist_slot(8, U)] = c_oot;
   }
 }
 

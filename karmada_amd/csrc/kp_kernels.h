@@ -2007,6 +2007,81 @@ KP_HD inline void body_reasons(const SnapView& s, const BatchView& bv, int b0, u
   out[i] = pair_reason(s, bv, bv.hdr[b], r);
 }
 
+// kp_fit_diagnosis_batch without the snapshot's bitset rows: item i's reason words
+// words[i][C] (body_reasons, then body_reasons_extra) reduced to the dense row
+// dense[i][hist_stride] that body_fit_hist writes (zeroed before the launch), by the calling
+// wave. Each code's count is a ballot's popcount; a KP_REASON_TAINT word goes to the bin of
+// the taint its argument indexes, with an atomic (a wave's lanes may share a bin).
+template <class BLK>
+KP_FI void body_reason_hist(const BLK& B, int i, const SnapView& s, const uint32_t* words, uint32_t* dense) {
+  const int U = s.n_taint_uid, ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  const uint32_t* o = words + (size_t)i * s.C;
+  uint32_t* row = dense + (size_t)i * hist_stride(U);
+  uint32_t n[9] = {};  // codes 0, 1, 3..8 and 255 (constant indices: registers)
+  for (int r0 = 0; r0 < s.C; r0 += ww) {  // (wave-uniform trip count: the ballots)
+    const int r = r0 + lane;
+    const uint32_t x = r < s.C ? o[r] : 2u;
+    const uint32_t code = x & 0xffu;
+    if (r < s.C && code == 2u) kp_atomic_add(row + hist_slot_uid(s.taint_uid[s.taint_off[r] + (int)(x >> 8)]), 1u);
+    n[0] += (uint32_t)popc64(B.wballot(code == 0u));
+    n[1] += (uint32_t)popc64(B.wballot(code == 1u));
+KP_UNROLL
+    for (int k = 3; k <= 8; k++) n[k - 1] += (uint32_t)popc64(B.wballot(code == (uint32_t)k));
+    n[8] += (uint32_t)popc64(B.wballot(code == 255u));
+  }
+  if (lane == 0) {
+    row[0] = n[0];
+    row[1] = n[8];
+    row[hist_slot(1, U)] = n[1];
+KP_UNROLL
+    for (int k = 3; k <= 8; k++) row[hist_slot(k, U)] = n[k - 1];
+  }
+}
+
+// The dense rows compacted into the diagnosis CSR: item i's bins are the non-zero words of
+// dense[i] from slot kHistBins0 on, in slot order. body_hist_count counts them (nbins[i]);
+// after the offsets scan body_hist_write stores each bin's reason code, taint_ref (uid_ref
+// of a taint bin, else 0) and count at offsets[i] + its position, a ballot and the count of
+// the lanes below within each 64-slot step (body_pack_wide's scheme), and the binding's
+// n_fit / n_deleting. One wave per item.
+template <class BLK>
+KP_FI void body_hist_count(const BLK& B, int i, int U, const uint32_t* dense, uint32_t* nbins) {
+  const int S = hist_stride(U);
+  const uint32_t* row = dense + (size_t)i * S;
+  uint32_t c = 0;
+  for (int k0 = kHistBins0; k0 < S; k0 += B.wwidth()) {
+    const int k = k0 + (B.lane() & (B.wwidth() - 1));
+    c += (uint32_t)popc64(B.wballot(k < S && row[k] != 0u));
+  }
+  if (B.lane() == 0) nbins[i] = c;
+}
+template <class BLK>
+KP_FI void body_hist_write(const BLK& B, int i, int U, const uint32_t* uid_ref, const uint32_t* dense,
+                           const uint64_t* offsets, uint32_t* reason, uint32_t* taint_ref, uint32_t* count,
+                           uint32_t* n_fit, uint32_t* n_del) {
+  const int S = hist_stride(U);
+  const uint32_t* row = dense + (size_t)i * S;
+  const uint64_t o = offsets[i];
+  uint32_t run = 0;
+  for (int k0 = kHistBins0; k0 < S; k0 += B.wwidth()) {
+    const int k = k0 + (B.lane() & (B.wwidth() - 1));
+    const uint32_t v = k < S ? row[k] : 0u;
+    const uint64_t m = B.wballot(v != 0u);
+    if (v != 0u) {
+      const uint64_t at = o + run + (uint32_t)popc64(m & B.wlt());
+      const bool taint = k >= hist_slot_uid(0) && k < hist_slot_uid(U);
+      reason[at] = k == hist_slot(1, U) ? 1u : taint ? 2u : (uint32_t)(k - U);
+      taint_ref[at] = taint ? uid_ref[k - hist_slot_uid(0)] : 0u;
+      count[at] = v;
+    }
+    run += (uint32_t)popc64(m);
+  }
+  if (B.lane() == 0) {
+    n_fit[i] = row[0];
+    n_del[i] = row[1];
+  }
+}
+
 // CSR offsets of the per-binding results: offsets[b] = sum of the counts of the
 // bindings before b whose status is OK (the others report no targets),
 // offsets[n] = total. Two launches over chunks of kOffChunk bindings: pass A

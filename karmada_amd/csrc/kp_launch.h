@@ -152,6 +152,9 @@ KP_HD inline int class_order_pad(int C) {
   return P;
 }
 KP_HD inline size_t class_order_lds_bytes(int P) { return kRedBytes + 8 * (size_t)P; }
+// k_fit_hist (body_fit_hist): per wave, the histogram bin of each distinct taint list.
+constexpr int kFitHistWaves = 4;  // one wave per diagnosed binding, as k_filter
+KP_HD inline size_t fit_hist_lds_bytes() { return 4 * (size_t)kTsetRowsMax; }
 // k_slow (body_slow): target bits, lds_area bytes for the small serial problems, lds_sort
 // for the candidate sorts.
 KP_HD inline size_t slow_lds_bytes(int Cp, int lds_area, int lds_sort) {

@@ -176,7 +176,24 @@ struct SnapView {
   const uint64_t* bkey;          // [bmask + 1] table keys (kBitsEmpty = free)
   const int32_t* bval;           // [bmask + 1] row of the key
   uint32_t bmask;
+  // FitError diagnosis (kp_fit_diagnosis_batch): the id of each taint's (key, value, effect)
+  // triple, parallel to taint_key, and per id the taint_ref that names it to the caller
+  // (caller cluster index | taint index << kTaintRefShift of the lowest caller index that
+  // carries the triple); ids ascend with their taint_ref. Null / 0 without taints; no
+  // scheduling kernel reads them.
+  const int32_t* taint_uid;
+  const uint32_t* uid_ref;       // [n_taint_uid]
+  int32_t n_taint_uid;
 };
+constexpr int kTaintRefShift = 18;  // (kMaxClusters = 2^18)
+// Dense FitError histogram row of one diagnosed binding, on the device only: [clusters that
+// fit | deleting clusters | KP_REASON_API | one word per taint uid | KP_REASON_AFFINITY ..
+// KP_REASON_OUT_OF_TREE], so the words from slot 2 on are the binding's bins in the order
+// the ABI states (reason code, then taint_ref).
+constexpr int kHistBins0 = 2;
+KP_HD inline int hist_stride(int n_uid) { return 9 + n_uid; }
+KP_HD inline int hist_slot(int code, int n_uid) { return code == 1 ? 2 : n_uid + code; }  // codes 1, 3..8
+KP_HD inline int hist_slot_uid(int uid) { return 3 + uid; }
 
 // Fixed bitset rows.
 enum : int32_t {

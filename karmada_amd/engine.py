@@ -37,7 +37,7 @@ EXPORTS = (
     "kp_pack_cache_get_stats",
     "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
     "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
-    "kp_schedule_affinities", "kp_filter_batch", "kp_filter_reasons", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
+    "kp_schedule_affinities", "kp_filter_batch", "kp_filter_reasons", "kp_fit_diagnosis_batch", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
     "kp_multi_create", "kp_multi_destroy", "kp_multi_last_error", "kp_multi_devices", "kp_multi_engine",
@@ -95,6 +95,7 @@ def load_library(path: str = LIB_PATH):
     L.kp_filter_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     L.kp_score_batch.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.kp_filter_reasons.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
+    L.kp_fit_diagnosis_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(api.kp_fit_diagnosis)]
     L.kp_max_available_replicas.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                                             C.POINTER(C.c_int32)]
     L.kp_max_available_component_sets.argtypes = [vp, vp, C.POINTER(api.kp_component), C.c_uint32,
@@ -461,6 +462,33 @@ class Batch:
             raise EngineError("kp_results_unpack: the packed results are inconsistent")
         return ci, rep
 
+    def fit_diagnosis_raw(self, bindings: Optional[Sequence[int]] = None) -> api.kp_fit_diagnosis:
+        """kp_fit_diagnosis_batch: the engine's arrays, valid until the next call on it."""
+        d = api.kp_fit_diagnosis()
+        eng = self.snap.engine
+        if bindings is None:
+            arr, n = None, 0
+        else:
+            n = len(bindings)
+            arr = (C.c_uint64 * max(1, n))(*bindings)
+        eng._check(eng.L.kp_fit_diagnosis_batch(eng.h, self.h, arr, n, C.byref(d)), "kp_fit_diagnosis_batch")
+        return d
+
+    def fit_diagnosis(self, bindings: Optional[Sequence[int]] = None) -> List[tuple]:
+        """The FitError reason histogram of each listed binding (strictly ascending batch
+        indices), or with bindings=None of every binding whose status was STATUS_FIT_ERROR in
+        this batch's last completed schedule call: (index, n_fit, n_deleting, [(reason,
+        taint_ref, count), ...]), the bins by reason code, then taint_ref. A REASON_TAINT
+        bin's taint_ref names the taint: caller cluster index | taint index << 18
+        (GenericScheduler.fit_errors resolves it)."""
+        d = self.fit_diagnosis_raw(bindings)
+        out = []
+        for i in range(d.n_bindings):
+            lo, hi = d.offsets[i], d.offsets[i + 1]
+            out.append((int(d.binding[i]), int(d.n_fit[i]), int(d.n_deleting[i]),
+                        [(int(d.reason[k]), int(d.taint_ref[k]), int(d.count[k])) for k in range(lo, hi)]))
+        return out
+
     def schedule(self, packed: bool = False) -> List[dict]:
         """Results as api.results_to_python dicts (cluster indices in snapshot input order).
         packed: through kp_schedule_batch_packed and kp_results_unpack (the same dicts)."""
@@ -671,6 +699,33 @@ class GenericScheduler:
         reasons = {cl["name"]: text(code, cl) for cl, code in zip(clusters, codes)
                    if code not in (api.REASON_FIT, api.REASON_DELETING)}
         return api.fit_error_message(len(clusters), reasons)
+
+    def fit_errors(self, bindings: Sequence[dict], clusters: Sequence[dict], results=None, filters=None,
+                   out_of_tree: Optional[str] = None) -> Dict[int, str]:
+        """FitError.Error() of every failed binding of one batch, {binding index: text}, from
+        one kp_fit_diagnosis_batch call (the reason histograms; no per-pair words cross the
+        bus). results: the ScheduleResults schedule(bindings) returned, whose STATUS_FIT_ERROR
+        entries are diagnosed; without them the batch is scheduled here first. clusters,
+        filters: as fit_error; out_of_tree: the one text of REASON_OUT_OF_TREE bins."""
+        b = Batch(self.snapshot, bindings, filters=filters)
+        try:
+            if results is None:
+                b.schedule_raw()
+                diag = b.fit_diagnosis()
+            else:
+                diag = b.fit_diagnosis([i for i, r in enumerate(results) if r.status == api.STATUS_FIT_ERROR])
+        finally:
+            b.close()
+        mask = (1 << api.TAINT_REF_CLUSTER_BITS) - 1
+        out = {}
+        for idx, _, _, bins in diag:
+            hist = {}
+            for reason, ref, count in bins:
+                word = reason | (ref >> api.TAINT_REF_CLUSTER_BITS) << 8
+                text = api.reason_text(word, clusters[ref & mask], out_of_tree)
+                hist[text] = hist.get(text, 0) + count
+            out[idx] = api.fit_error_histogram_message(len(clusters), hist)
+        return out
 
     def score(self, bindings: Sequence[dict]) -> List[List[int]]:
         """Summed plugin scores per (binding, cluster) (prioritizeClusters)."""
