@@ -244,7 +244,7 @@ int select(stream_t, int which, const KArgs& a, size_t smem, int cap, const Sele
       // KP_CPUSIM_SLOW_GRID=<g> narrows the grid, to replay such orders here.
       if (kp_env_flag("KP_CPUSIM_SLOW_SHUFFLE")) {
         uint64_t r = (uint64_t)kp_env_int("KP_CPUSIM_SLOW_SHUFFLE", 0) * 0x9E3779B97F4A7C15ull + 1;
-        const int ns = (int)std::min<uint32_t>(a.stats[0], (uint32_t)a.n);
+        const int ns = (int)std::min<uint32_t>(a.stats[KS_SLOW_TOTAL], (uint32_t)a.n);
         for (int i = ns - 1; i > 0; i--) {
           r ^= r << 13, r ^= r >> 7, r ^= r << 17;
           std::swap(a.slow_ids[i], a.slow_ids[(int)(r % (uint64_t)(i + 1))]);

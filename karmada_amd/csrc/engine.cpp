@@ -18,6 +18,7 @@
 #include <mutex>
 #include <new>
 #include <tuple>
+#include <type_traits>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -201,19 +202,36 @@ void* pinned_get(size_t bytes, size_t* got) {
 
 // One device allocation carved into aligned sub-buffers. pool_dev >= 0: the
 // allocation comes from (and returns to) the batch-buffer pool of that device.
+// A sub-buffer filled from host data is registered with its source (the second add):
+// upload() then copies what was registered, so the bytes reserved and the bytes copied
+// come from one count and the destination's element type.
 struct Arena {
-  std::vector<std::pair<void**, size_t>> req;
+  struct Req {
+    void** p;
+    size_t bytes;     // reserved
+    const void* src;  // host source, or null for a work buffer
+    size_t src_bytes;
+  };
+  std::vector<Req> req;
   void* base = nullptr;
   size_t total = 0;
   int pool_dev = -1;
   size_t got = 0;
   template <class T>
   void add(T** p, size_t count) {
-    req.push_back({(void**)p, count * sizeof(T)});
+    req.push_back({(void**)p, count * sizeof(T), nullptr, 0});
   }
+  // *p[0, count) = src[0, count) at upload(); max(count, min_count) elements are reserved
+  // (a list that may be empty keeps a valid pointer). src must stay alive until the
+  // stream upload() ran on is synchronised.
+  template <class T>
+  void add(T** p, const std::type_identity_t<T>* src, size_t count, size_t min_count = 0) {
+    req.push_back({(void**)p, std::max(count, min_count) * sizeof(T), src, count * sizeof(T)});
+  }
+  static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
   int alloc() {
     total = 0;
-    for (auto& r : req) total += (r.second + 255) & ~(size_t)255;
+    for (auto& r : req) total += pad(r.bytes);
     if (total == 0) total = 256;
     if (pool_dev >= 0) base = buf_pool().get(pool_dev, total, &got);
     if (!base) {
@@ -222,8 +240,16 @@ struct Arena {
     }
     char* p = (char*)base;
     for (auto& r : req) {
-      *r.first = p;
-      p += (r.second + 255) & ~(size_t)255;
+      *r.p = p;
+      p += pad(r.bytes);
+    }
+    return 0;
+  }
+  // The registered host sources copied to their sub-buffers on `st` (after alloc()).
+  int upload(dev::stream_t st) {
+    for (auto& r : req) {
+      if (r.src && dev::h2d(*r.p, r.src, r.src_bytes, st)) return -1;
+      r.src = nullptr;  // (copied once: the source need not outlive the caller's sync)
     }
     return 0;
   }
@@ -283,12 +309,33 @@ struct NoInitAlloc : std::allocator<T> {
 // ============================================================================
 // Engine / snapshot / batch objects
 // ============================================================================
+// The engine's events (kp_engine::ev), one per event a schedule call records; BEGIN / END
+// pairs time a stage for kp_last_stage_times, the others order the three streams.
+enum : int {
+  EV_FILLS = 0,       // stream: the counters are cleared (every kernel waits for it)
+  EV_SELECT_BEGIN,    // stream: the rows are complete ...
+  EV_SELECT_END,      // ... to the end of the last select kernel and k_slow
+  EV_ROWS_BEGIN,      // stream2: the estimator rows and the filter ...
+  EV_ROWS_END,        // ... complete (stream and stream3 wait for it)
+  EV_CLASS_ROWS,      // stream2: every class row is written (k_class_order's input)
+  EV_CLASS_ORDER,     // stream3: k_class_order done (stream2 waits for it)
+  EV_SEL_ALL_BEGIN,   // stream2: the SEL_ALL kernels ...
+  EV_SEL_ALL_END,     // ... (k_slow and the results wait for it)
+  EV_SLOW_END,        // stream3: k_slow done (the results wait for it)
+  EV_TOP_LARGE,       // stream3: k_select_top's large slice done (its fallbacks follow on stream2)
+  EV_TOP_BEGIN,       // stream2: k_select_top's launches ...
+  EV_TOP_END,
+  EV_CLUSTER_BEGIN,   // stream3: the cluster-spread kernels ...
+  EV_CLUSTER_END,
+  kEngineEvents
+};
+
 struct kp_engine {
   int device = 0;
   dev::stream_t stream = nullptr;   // select kernels, copies (the batch's result order)
   dev::stream_t stream2 = nullptr;  // pair kernel, then the SEL_ALL select kernel
   dev::stream_t stream3 = nullptr;  // the cluster-spread select kernel, beside the other selects
-  dev::event_t ev[16] = {};
+  dev::event_t ev[kEngineEvents] = {};
   std::string err;
   kp_stage_times times{};
   struct {  // kp_schedule_affinities results
@@ -319,7 +366,7 @@ struct kp_engine {
   struct KProf {
     const char* name;
     uint64_t units;  // bindings (or rows) the launch covered
-    int units_stat;  // >= 0: the count is device-side, h_stats[units_stat]
+    int units_stat;  // >= 0: the count is device-side, h_stats[units_stat] (KS_*)
   };
   bool prof = false;
   uint64_t submit_seq = 0;  // schedule calls submitted on this engine (stage timing validity)
@@ -448,11 +495,7 @@ struct kp_batch {
   KArgs* d_kargs = nullptr;
   KArgs* h_kargs = nullptr;
   size_t h_kargs_bytes = 0;
-  uint32_t h_stats[20] = {};  // [0..7] slow-path counts, [8] component-set simulation overflow, [9] k_select_top
-                              // fallbacks, [10] / [11] cluster- / region-spread bindings selected over the class order,
-                              // [12] / [13] k_spread_order's fallback list lengths, [14] k_region_a_order's
-                              // [16] k_select_top's capacity overflows (the top_cap_mid launch)
-                              // [17] bindings k_region_wide scheduled or errored
+  uint32_t h_stats[kStatSlots] = {};  // the counters after a schedule call (KS_*, kp_launch.h)
   uint32_t* out_idx = nullptr;
   int32_t* out_rep = nullptr;
   uint64_t* offsets_d = nullptr;
@@ -850,6 +893,7 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
   const int K = (int)s->keys.names.size(), AW = ((int)s->gvk.names.size() + 63) / 64,
             R = (int)s->res.names.size();
   SnapView& v = s->view;
+  v = SnapView{};  // (an update uploads again: the optional tables start out null)
   v.C = C;
   v.Cp = Cp;
   v.W = s->W;
@@ -859,10 +903,6 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
   v.n_tmpl = s->n_tmpl;
   v.n_regions = (int)s->regions.names.size();
   Arena& a = s->dev;
-  uint32_t *d_flags, *d_perm;
-  int32_t *d_prov, *d_reg, *d_regidx, *d_zoff, *d_zid, *d_lbl, *d_toff, *d_tk, *d_tv, *d_te, *d_mtid, *d_mcnt;
-  int64_t *d_pint, *d_rint, *d_allowed, *d_avail, *d_tmpl, *d_qa;
-  uint64_t* d_api;
   // taint lists deduplicated: one TaintToleration answer per distinct list and binding
   std::vector<int32_t> tset(Cp, 0), trep;
   {
@@ -884,7 +924,6 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
     }
     if (trep.empty()) trep.push_back(0);
   }
-  int32_t *d_tset, *d_trep, *d_mt = nullptr;
   // FitError diagnosis: one id per distinct (key, value, effect) triple, i.e. per distinct
   // taint text, and the taint_ref that names it: the lowest caller cluster index that carries
   // the triple with its first position there. Ids are numbered in taint_ref order, so a
@@ -904,8 +943,6 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
     for (size_t t = 0; t < tuid.size(); t++)
       tuid[t] = (int32_t)(std::lower_bound(uref.begin(), uref.end(), ref_of[triple((int)t)]) - uref.begin());
   }
-  int32_t* d_tuid = nullptr;
-  uint32_t* d_uref = nullptr;
   // Cluster bitsets of the filter predicates (kp_filter.h; SnapView::bits).
   std::vector<uint64_t> bits, bkey;
   std::vector<int32_t> bval;
@@ -970,8 +1007,6 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
       }
     }
   }
-  uint64_t *d_bits = nullptr, *d_bkey = nullptr;
-  int32_t* d_bval = nullptr;
   // model node counts per (template, cluster): the fast estimator's dense form
   std::vector<int32_t> mt;
   {
@@ -988,113 +1023,51 @@ int upload_snapshot(kp_engine* e, kp_snapshot* s) {
       for (size_t i = 0; i < acc.size(); i++) mt[i] = (int32_t)std::min<int64_t>(acc[i], kInt32Max);
     }
   }
-  a.add(&d_flags, Cp);
-  a.add(&d_tset, Cp);
-  a.add(&d_trep, trep.size());
-  if (!mt.empty()) a.add(&d_mt, mt.size());
-  a.add(&d_perm, Cp);
-  a.add(&d_prov, Cp);
-  a.add(&d_reg, Cp);
-  a.add(&d_regidx, Cp);
-  a.add(&d_zoff, C + 1);
-  a.add(&d_zid, s->zone_ids.size());
-  a.add(&d_lbl, s->label_val.size());
-  a.add(&d_toff, C + 1);
-  a.add(&d_tk, s->taint_key.size());
-  a.add(&d_tv, s->taint_val.size());
-  a.add(&d_te, s->taint_eff.size());
-  if (!tuid.empty()) {
-    a.add(&d_tuid, tuid.size());
-    a.add(&d_uref, uref.size());
-  }
-  a.add(&d_mtid, s->mg_tid.size());
-  a.add(&d_mcnt, s->mg_cnt.size());
-  a.add(&d_pint, Cp);
-  a.add(&d_rint, Cp);
-  a.add(&d_allowed, Cp);
-  a.add(&d_avail, s->avail.size());
-  a.add(&d_qa, s->qa.size());
-  a.add(&d_tmpl, s->tmpl.size());
-  a.add(&d_api, s->api_bits.size());
-  if (n_bits) {
-    a.add(&d_bits, bits.size());
-    a.add(&d_bkey, bkey.size());
-    a.add(&d_bval, bval.size());
-  }
-  HIPCHK(a.alloc());
   std::vector<uint32_t> permp(Cp, 0);
   for (int r = 0; r < C; r++) permp[r] = s->perm[r];
-  auto up = [&](void* d, const void* h, size_t bytes) { return dev::h2d(d, h, bytes, e->stream); };
-  HIPCHK(up(d_flags, s->flags.data(), 4 * Cp));
-  HIPCHK(up(d_tset, tset.data(), 4 * Cp));
-  HIPCHK(up(d_trep, trep.data(), 4 * trep.size()));
-  if (!mt.empty()) HIPCHK(up(d_mt, mt.data(), 4 * mt.size()));
-  HIPCHK(up(d_perm, permp.data(), 4 * Cp));
-  HIPCHK(up(d_prov, s->provider.data(), 4 * Cp));
-  HIPCHK(up(d_reg, s->region.data(), 4 * Cp));
-  HIPCHK(up(d_regidx, s->region_idx.data(), 4 * Cp));
-  HIPCHK(up(d_zoff, s->zone_off.data(), 4 * (C + 1)));
-  HIPCHK(up(d_zid, s->zone_ids.data(), 4 * s->zone_ids.size()));
-  HIPCHK(up(d_lbl, s->label_val.data(), 4 * s->label_val.size()));
-  HIPCHK(up(d_toff, s->taint_off.data(), 4 * (C + 1)));
-  HIPCHK(up(d_tk, s->taint_key.data(), 4 * s->taint_key.size()));
-  HIPCHK(up(d_tv, s->taint_val.data(), 4 * s->taint_val.size()));
-  HIPCHK(up(d_te, s->taint_eff.data(), 4 * s->taint_eff.size()));
+  a.add(&v.flags, s->flags.data(), Cp);
+  a.add(&v.taint_set, tset.data(), Cp);
+  a.add(&v.tset_rep, trep.data(), trep.size());
+  if (!mt.empty()) a.add(&v.mt_cnt, mt.data(), mt.size());
+  a.add(&v.perm, permp.data(), Cp);
+  a.add(&v.provider, s->provider.data(), Cp);
+  a.add(&v.region, s->region.data(), Cp);
+  a.add(&v.region_idx, s->region_idx.data(), Cp);
+  a.add(&v.zone_off, s->zone_off.data(), C + 1);
+  a.add(&v.zone_ids, s->zone_ids.data(), s->zone_ids.size());
+  a.add(&v.label_val, s->label_val.data(), s->label_val.size());
+  a.add(&v.taint_off, s->taint_off.data(), C + 1);
+  a.add(&v.taint_key, s->taint_key.data(), s->taint_key.size());
+  a.add(&v.taint_val, s->taint_val.data(), s->taint_val.size());
+  a.add(&v.taint_eff, s->taint_eff.data(), s->taint_eff.size());
   if (!tuid.empty()) {
-    HIPCHK(up(d_tuid, tuid.data(), 4 * tuid.size()));
-    HIPCHK(up(d_uref, uref.data(), 4 * uref.size()));
+    a.add(&v.taint_uid, tuid.data(), tuid.size());
+    a.add(&v.uid_ref, uref.data(), uref.size());
   }
-  HIPCHK(up(d_mtid, s->mg_tid.data(), 4 * s->mg_tid.size()));
-  HIPCHK(up(d_mcnt, s->mg_cnt.data(), 4 * s->mg_cnt.size()));
-  HIPCHK(up(d_pint, s->provider_int.data(), 8 * Cp));
-  HIPCHK(up(d_rint, s->region_int.data(), 8 * Cp));
-  HIPCHK(up(d_allowed, s->allowed.data(), 8 * Cp));
-  HIPCHK(up(d_avail, s->avail.data(), 8 * s->avail.size()));
-  HIPCHK(up(d_qa, s->qa.data(), 8 * s->qa.size()));
-  HIPCHK(up(d_tmpl, s->tmpl.data(), 8 * s->tmpl.size()));
-  HIPCHK(up(d_api, s->api_bits.data(), 8 * s->api_bits.size()));
+  a.add(&v.mg_tid, s->mg_tid.data(), s->mg_tid.size());
+  a.add(&v.mg_cnt, s->mg_cnt.data(), s->mg_cnt.size());
+  a.add(&v.provider_int, s->provider_int.data(), Cp);
+  a.add(&v.region_int, s->region_int.data(), Cp);
+  a.add(&v.allowed, s->allowed.data(), Cp);
+  a.add(&v.avail, s->avail.data(), s->avail.size());
+  a.add(&v.qa, s->qa.data(), s->qa.size());
+  a.add(&v.tmpl, s->tmpl.data(), s->tmpl.size());
+  a.add(&v.api_bits, s->api_bits.data(), s->api_bits.size());
   if (n_bits) {
-    HIPCHK(up(d_bits, bits.data(), 8 * bits.size()));
-    HIPCHK(up(d_bkey, bkey.data(), 8 * bkey.size()));
-    HIPCHK(up(d_bval, bval.data(), 4 * bval.size()));
+    a.add(&v.bits, bits.data(), bits.size());
+    a.add(&v.bkey, bkey.data(), bkey.size());
+    a.add(&v.bval, bval.data(), bval.size());
   }
+  HIPCHK(a.alloc());
+  HIPCHK(a.upload(e->stream));
   HIPCHK(dev::sync(e->stream));
-  v.flags = d_flags;
-  v.perm = d_perm;
-  v.provider = d_prov;
-  v.region = d_reg;
-  v.region_idx = d_regidx;
-  v.provider_int = d_pint;
-  v.region_int = d_rint;
-  v.zone_off = d_zoff;
-  v.zone_ids = d_zid;
-  v.label_val = d_lbl;
-  v.taint_off = d_toff;
-  v.taint_key = d_tk;
-  v.taint_val = d_tv;
-  v.taint_eff = d_te;
-  v.taint_set = d_tset;
-  v.tset_rep = d_trep;
   v.n_tsets = (int32_t)trep.size();
-  v.taint_uid = d_tuid;
-  v.uid_ref = d_uref;
   v.n_taint_uid = (int32_t)uref.size();
-  v.api_bits = d_api;
-  v.allowed = d_allowed;
-  v.avail = d_avail;
-  v.qa = d_qa;
   v.kmax = kmax;
-  v.mg_tid = d_mtid;
-  v.mg_cnt = d_mcnt;
-  v.tmpl = d_tmpl;
-  v.mt_cnt = d_mt;
-  v.bits = d_bits;
   v.n_bits = n_bits;
   v.br_api = br_api;
   v.br_tset = br_tset;
   v.br_lex = br_lex;
-  v.bkey = d_bkey;
-  v.bval = d_bval;
   v.bmask = n_bits ? (uint32_t)(bkey.size() - 1) : 0u;
   s->est_kind = snapshot_est_kind(s);
   return KP_OK;
@@ -3149,112 +3122,122 @@ int kp_pack_cache_get_stats(const kp_pack_cache* c, kp_pack_cache_stats* out) {
   out->last_hits = c->last_hits;
   return KP_OK;
 }
-static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
-                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est, const kp_filter_answers* flt) {
-  if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
-  if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
-  (void)dev::set_device(e->device);
-  kp_snapshot* s = const_cast<kp_snapshot*>(sc);
-  // The other estimators' rows (kp_estimates), checked and brought into rank order with the
-  // device rows' padding (-1: no answer) before anything is packed; none: est stays null.
-  std::vector<int32_t> est_rows;
-  if (est && est->n_rows == 0) est = nullptr;
-  if (est) {
-    auto bad = [&](std::string why) {
-      e->err = "kp_batch_create_estimates: " + why;
-      return KP_EINVAL;
-    };
-    if (est->n_clusters != (uint64_t)s->C)
-      return bad("n_clusters is " + std::to_string(est->n_clusters) + ", the snapshot holds " + std::to_string(s->C) +
-                 " clusters");
-    if (!est->rows || (n && !est->row_of)) return bad("rows or row_of is null");
-    if (est->n_rows > (uint32_t)INT32_MAX) return bad("more than 2^31 - 1 rows");
-    for (uint64_t i = 0; i < n; i++)
-      if (est->row_of[i] < -1 || est->row_of[i] >= (int64_t)est->n_rows)
-        return bad("row_of[" + std::to_string(i) + "] = " + std::to_string(est->row_of[i]) + " is outside -1.." +
-                   std::to_string((int64_t)est->n_rows - 1));
-    est_rows.assign((size_t)est->n_rows * s->Cp, -1);
-    for (uint32_t r = 0; r < est->n_rows; r++) {
-      const int32_t* src = est->rows + (size_t)r * s->C;
-      int32_t* dst = est_rows.data() + (size_t)r * s->Cp;
-      for (int k = 0; k < s->C; k++) {
-        const int32_t v = src[s->perm[k]];
-        if (v < -1)
-          return bad("rows[" + std::to_string(r) + "][" + std::to_string(s->perm[k]) + "] = " + std::to_string(v) +
-                     " is below -1 (UnauthenticReplica)");
-        dst[k] = v;
-      }
+// kp_batch_create runs in stages (take_estimates ... upload, in that order); CreateCtx is
+// what they share. Every host array the arena uploads from and no kp_batch member keeps
+// lives here, so it outlives the upload's sync by construction.
+namespace {
+struct CreateCtx {
+  kp_engine* e;
+  kp_snapshot* s;
+  const kp_binding* bindings;
+  uint64_t n;
+  const kp_estimates* est;         // null once found empty
+  const kp_filter_answers* flt;    // null once found empty
+  kp_batch* bt = nullptr;
+  std::vector<int32_t> est_rows;   // kp_estimates rows by cluster rank, [n_rows][Cp]
+  std::vector<uint64_t> flt_rows;  // kp_filter_answers rows by cluster rank, [n_rows][W]
+  std::vector<FltPair> flt_list;   // the bindings that have a filter row
+  uint32_t flt_plugins = 0;
+  std::vector<int32_t> rep;        // d_crep's source: crep, -1 in the component-set classes
+  std::vector<int64_t> sets_off;   // per cluster rank, its node-run scratch offset
+  bool with_orders = false;
+  std::chrono::steady_clock::time_point tp0, tp1, tp2;
+};
+}  // namespace
+
+// What the two optional inputs' checks share: the n_clusters check that opens them and the
+// n_rows bound and row_of range that close them; each input's own checks come between.
+static int bad_answers(CreateCtx& c, const char* who, const std::string& why) {
+  c.e->err = std::string(who) + ": " + why;
+  return KP_EINVAL;
+}
+static int check_clusters(CreateCtx& c, const char* who, uint64_t n_clusters) {
+  if (n_clusters == (uint64_t)c.s->C) return KP_OK;
+  return bad_answers(c, who, "n_clusters is " + std::to_string(n_clusters) + ", the snapshot holds " +
+                                 std::to_string(c.s->C) + " clusters");
+}
+static int check_row_of(CreateCtx& c, const char* who, uint32_t n_rows, const int32_t* row_of) {
+  if (n_rows > (uint32_t)INT32_MAX) return bad_answers(c, who, "more than 2^31 - 1 rows");
+  for (uint64_t i = 0; i < c.n; i++)
+    if (row_of[i] < -1 || row_of[i] >= (int64_t)n_rows)
+      return bad_answers(c, who, "row_of[" + std::to_string(i) + "] = " + std::to_string(row_of[i]) +
+                                     " is outside -1.." + std::to_string((int64_t)n_rows - 1));
+  return KP_OK;
+}
+
+// Stage 1a: the other estimators' rows (kp_estimates), checked and brought into rank order
+// with the device rows' padding (-1: no answer) before anything is packed; none: est null.
+static int take_estimates(CreateCtx& c) {
+  const kp_estimates* est = c.est;
+  kp_snapshot* s = c.s;
+  if (est && est->n_rows == 0) est = c.est = nullptr;
+  if (!est) return KP_OK;
+  const char* who = "kp_batch_create_estimates";
+  if (int rc = check_clusters(c, who, est->n_clusters)) return rc;
+  if (!est->rows || (c.n && !est->row_of)) return bad_answers(c, who, "rows or row_of is null");
+  if (int rc = check_row_of(c, who, est->n_rows, est->row_of)) return rc;
+  c.est_rows.assign((size_t)est->n_rows * s->Cp, -1);
+  for (uint32_t r = 0; r < est->n_rows; r++) {
+    const int32_t* src = est->rows + (size_t)r * s->C;
+    int32_t* dst = c.est_rows.data() + (size_t)r * s->Cp;
+    for (int k = 0; k < s->C; k++) {
+      const int32_t v = src[s->perm[k]];
+      if (v < -1)
+        return bad_answers(c, who, "rows[" + std::to_string(r) + "][" + std::to_string(s->perm[k]) + "] = " +
+                                       std::to_string(v) + " is below -1 (UnauthenticReplica)");
+      dst[k] = v;
     }
   }
-  // The out-of-tree filter verdicts (kp_filter_answers), checked and brought into rank order
-  // (dev_row bit rank = caller_row bit perm[rank]; W words a row, zero bits in the padding,
-  // caller bits at or above C never read), and the bindings that have a row.
-  std::vector<uint64_t> flt_rows;
-  std::vector<FltPair> flt_list;
-  const uint32_t flt_plugins = flt ? flt->n_plugins : 0;
-  if (flt && flt->n_rows == 0) flt = nullptr;
-  if (flt) {
-    auto bad = [&](std::string why) {
-      e->err = "kp_batch_create_filters: " + why;
-      return KP_EINVAL;
-    };
-    if (flt->n_clusters != (uint64_t)s->C)
-      return bad("n_clusters is " + std::to_string(flt->n_clusters) + ", the snapshot holds " + std::to_string(s->C) +
-                 " clusters");
-    if (!flt->rows) return bad("rows is null");
-    if (n && !flt->row_of) return bad("row_of is null");
-    if (flt->n_plugins == 0) return bad("n_rows is " + std::to_string(flt->n_rows) + " with n_plugins == 0");
-    if (flt->n_rows > (uint32_t)INT32_MAX) return bad("more than 2^31 - 1 rows");
-    for (uint64_t i = 0; i < n; i++) {
-      const int32_t r = flt->row_of[i];
-      if (r < -1 || r >= (int64_t)flt->n_rows)
-        return bad("row_of[" + std::to_string(i) + "] = " + std::to_string(r) + " is outside -1.." +
-                   std::to_string((int64_t)flt->n_rows - 1));
-      if (r >= 0) flt_list.push_back(FltPair{(int32_t)i, r});
-    }
-    if (!flt_list.empty()) {  // (rows that no binding uses: nothing to merge)
-      const size_t Wc = ((size_t)s->C + 63) / 64;
-      flt_rows.assign((size_t)flt->n_rows * s->W, 0);
-      for (uint32_t r = 0; r < flt->n_rows; r++) {
-        const uint64_t* src = flt->rows + (size_t)r * Wc;
-        uint64_t* dst = flt_rows.data() + (size_t)r * s->W;
-        for (int k = 0; k < s->C; k++) {
-          const uint32_t c = s->perm[k];
-          dst[k >> 6] |= ((src[c >> 6] >> (c & 63)) & 1) << (k & 63);
-        }
-      }
+  return KP_OK;
+}
+
+// Stage 1b: the out-of-tree filter verdicts (kp_filter_answers), checked and brought into
+// rank order (dev_row bit rank = caller_row bit perm[rank]; W words a row, zero bits in the
+// padding, caller bits at or above C never read), and the bindings that have a row.
+static int take_filters(CreateCtx& c) {
+  const kp_filter_answers* flt = c.flt;
+  kp_snapshot* s = c.s;
+  c.flt_plugins = flt ? flt->n_plugins : 0;
+  if (flt && flt->n_rows == 0) flt = c.flt = nullptr;
+  if (!flt) return KP_OK;
+  const char* who = "kp_batch_create_filters";
+  if (int rc = check_clusters(c, who, flt->n_clusters)) return rc;
+  if (!flt->rows) return bad_answers(c, who, "rows is null");
+  if (c.n && !flt->row_of) return bad_answers(c, who, "row_of is null");
+  if (flt->n_plugins == 0)
+    return bad_answers(c, who, "n_rows is " + std::to_string(flt->n_rows) + " with n_plugins == 0");
+  if (int rc = check_row_of(c, who, flt->n_rows, flt->row_of)) return rc;
+  for (uint64_t i = 0; i < c.n; i++)
+    if (flt->row_of[i] >= 0) c.flt_list.push_back(FltPair{(int32_t)i, flt->row_of[i]});
+  if (c.flt_list.empty()) return KP_OK;  // (rows that no binding uses: nothing to merge)
+  const size_t Wc = ((size_t)s->C + 63) / 64;
+  c.flt_rows.assign((size_t)flt->n_rows * s->W, 0);
+  for (uint32_t r = 0; r < flt->n_rows; r++) {
+    const uint64_t* src = flt->rows + (size_t)r * Wc;
+    uint64_t* dst = c.flt_rows.data() + (size_t)r * s->W;
+    for (int k = 0; k < s->C; k++) {
+      const uint32_t cl = s->perm[k];
+      dst[k >> 6] |= ((src[cl >> 6] >> (cl & 63)) & 1) << (k & 63);
     }
   }
-  auto* bt = new kp_batch();
-  std::unique_ptr<kp_batch> guard(bt);
-  bt->snap = s;
-  bt->B = (int)n;
-  bt->hdr.resize(n);
-  bt->flt_plugins = flt_plugins;
-  bt->l_flt = std::move(flt_list);
-  const auto tp0 = std::chrono::steady_clock::now();
-  if (s->opts.multiple_pod_templates_scheduling)
-    for (uint64_t i = 0; i < n; i++)
-      if (bindings[i].n_components > 0 && !bindings[i].components) {
-        e->err = "kp_batch_create: binding " + std::to_string(i) +
-                 " has n_components > 0 but no components (the MultiplePodTemplatesScheduling gate reads them)";
-        return KP_EINVAL;
-      }
-  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache, est ? est->row_of : nullptr)) {
-    e->err = bt->err.empty() ? "batch pools exceed 2^31 entries" : bt->err;
-    return KP_ENOTSUP;
-  }
-  // the selection lists from the routes (binding order within each kind). SEL_ALL:
-  // [non-StaticWeight | StaticWeight]; the non-StaticWeight ones split by the subset
-  // they likely need (k_select_top's small LDS slice first: a DynamicWeight /
-  // Aggregated subset holds the scheduled clusters and about as many walked parties
-  // as the target replicas), each part grouped by estimator class (counting sort,
-  // stable: the workgroups resident at any moment then cover a short run of the list,
-  // i.e. few classes, whose orders and rows stay in every XCD's L2; k_select_top
-  // 1.23 -> 1.10 ms at config 3, mapping each XCD to one contiguous run of the list
-  // instead was slower, 1.33 ms); StaticWeight bindings the class-level kernel covers
-  // (bits mode) before the others.
+  return KP_OK;
+}
+
+// Stage 2: the selection lists from the routes (binding order within each kind), and the
+// 256-region refusal. SEL_ALL:
+// [non-StaticWeight | StaticWeight]; the non-StaticWeight ones split by the subset
+// they likely need (k_select_top's small LDS slice first: a DynamicWeight /
+// Aggregated subset holds the scheduled clusters and about as many walked parties
+// as the target replicas), each part grouped by estimator class (counting sort,
+// stable: the workgroups resident at any moment then cover a short run of the list,
+// i.e. few classes, whose orders and rows stay in every XCD's L2; k_select_top
+// 1.23 -> 1.10 ms at config 3, mapping each XCD to one contiguous run of the list
+// instead was slower, 1.33 ms); StaticWeight bindings the class-level kernel covers
+// (bits mode) before the others.
+static int route_lists(CreateCtx& c) {
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const uint64_t n = c.n;
   {
     const std::vector<uint8_t>& rt = bt->route;
     const size_t ncls = std::max<size_t>(1, bt->crep.size());
@@ -3299,10 +3282,12 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     bt->n_top_small = n_small;
     bt->n_static = n_stat_ok;
   }
+  bt->l_all_cls.resize(bt->l_all.size());
+  for (size_t i = 0; i < bt->l_all.size(); i++) bt->l_all_cls[i] = bt->bcls[bt->l_all[i]];
   bt->l_slow = bt->l_all;
   bt->l_slow.insert(bt->l_slow.end(), bt->l_cluster.begin(), bt->l_cluster.end());
   if (s->view.n_regions > kRegionMax && !bt->l_region.empty()) {
-    e->err = "region spread over more than 256 regions is not supported";
+    c.e->err = "region spread over more than 256 regions is not supported";
     return KP_ENOTSUP;
   }
   // the region bindings that can need k_region_wide, by their row in l_region (rsel, rnsel
@@ -3312,26 +3297,25 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     if (h.cluster_max > kSmallMax || ((h.flags & BF_DUP_TARGETS) && h.tgt_cnt > kTgtSmallMax))
       bt->l_region_wide.push_back((int32_t)j);
   }
-  if (!bt->l_region_wide.empty()) {
-    // its candidate sort in LDS when the keys fit beside the rest (KP_WIDE_LDS=0, a
-    // diagnostic, keeps them in the global slot), as k_slow's
-    int P = 1;
-    while (P < s->Cp) P <<= 1;
-    if (kp_env_int("KP_WIDE_LDS", 1) != 0 && region_wide_lds_bytes(s->Cp, s->view.n_regions, 8 * P) <= e->max_lds)
-      bt->wide_sort = 8 * P;
-  }
+  return KP_OK;
+}
+
+// Stage 3: the serial kernels' sizes (k_slow, k_region_wide): result capacity, LDS areas,
+// scratch slots and grids, with their env knobs; and the batch's LDS check, which reads
+// k_region_wide's sort area.
+static int size_serial(CreateCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  int P = 1;
+  while (P < s->Cp) P <<= 1;
+  // k_region_wide's candidate sort in LDS when the keys fit beside the rest (KP_WIDE_LDS=0,
+  // a diagnostic, keeps them in the global slot), as k_slow's
+  if (!bt->l_region_wide.empty() && kp_env_int("KP_WIDE_LDS", 1) != 0 &&
+      region_wide_lds_bytes(s->Cp, s->view.n_regions, 8 * P) <= e->max_lds)
+    bt->wide_sort = 8 * P;
   if (batch_lds_check(e, s, bt)) return KP_ENOTSUP;
   bt->n_regions = s->view.n_regions;
-  auto pad1 = [](auto& v) {
-    if (v.empty()) v.resize(1);
-  };
-  pad1(bt->ipool);
-  pad1(bt->lpool);
-  pad1(bt->tols);
-  pad1(bt->progs);
-  pad1(bt->instrs);
-  const int B = bt->B ? bt->B : 1;
-  const int nr = (int)bt->l_region.size(), R = std::max(1, s->view.n_regions);
   const int max_tgt = bt->max_tgt, max_tiers = bt->max_tiers;
   // SerialAssign's result list: every candidate once, plus, per overflow tier, the
   // spec.Clusters entries MergeTargetClusters appends (common.go:97-139; util/binding.go:91-115).
@@ -3340,8 +3324,6 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     size_t b = sizeof(Item) * (size_t)max_tgt + serial_scratch_bytes(2 * max_tgt + 16) + 64;
     bt->slow_lds = b <= 32768 ? (int)((b + 15) & ~(size_t)15) : 0;
   }
-  int P = 1;
-  while (P < s->Cp) P <<= 1;
   {  // LDS for the candidate sorts (bitonic keys, then the sort.Sort emulation)
     const size_t base = slow_lds_bytes(s->Cp, bt->slow_lds, 0);
     const size_t sel = 3072 + 8 * (size_t)sel_all_ecap(s->Cp) + 64;  // SelScratch of the tie route
@@ -3366,59 +3348,17 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
     bt->wide_grid = (int)std::min<size_t>({(size_t)64, bt->l_region_wide.size(), fit});
   }
   bt->fast_ok = batch_fast_ok(bt);
-  Arena& a = bt->dev;
-  a.pool_dev = e->device;
-  BindHdr* d_hdr;
-  int32_t* d_ipool;
-  int64_t* d_lpool;
-  Tol* d_tols;
-  Prog* d_progs;
-  Instr* d_instrs;
-  a.add(&d_hdr, B);
-  a.add(&d_ipool, bt->ipool.size());
-  a.add(&d_lpool, bt->lpool.size());
-  a.add(&d_tols, bt->tols.size());
-  a.add(&d_progs, bt->progs.size());
-  a.add(&d_instrs, bt->instrs.size());
-  a.add(&bt->fmask, (size_t)B * s->W);
-  a.add(&bt->d_bcls, B);
-  a.add(&bt->d_crep, bt->crep.size());
-  a.add(&bt->cls_rows, bt->crep.size() * (size_t)s->Cp);
-  a.add(&bt->d_all, std::max<size_t>(1, bt->l_all.size()));
-  a.add(&bt->d_all_cls, std::max<size_t>(1, bt->l_all.size()));
-  a.add(&bt->d_cluster, std::max<size_t>(1, bt->l_cluster.size()));
-  a.add(&bt->d_region, std::max<size_t>(1, bt->l_region.size()));
-  a.add(&bt->d_slowlist, std::max<size_t>(1, bt->l_slow.size()));
-  a.add(&bt->d_cs, std::max<size_t>(1, bt->l_cs.size()));
-  a.add(&bt->status, B);
-  a.add(&bt->errc, B);
-  a.add(&bt->slow, B);
-  a.add(&bt->arg, B);
-  a.add(&bt->start, B);
-  a.add(&bt->count, B);
-  a.add(&bt->counter, 1);
-  a.add(&bt->stats, 20);
-  a.add(&bt->d_kargs, kArgSlots);
-#if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
-  a.add(&bt->dbg, kDbgSlots * kDbgSpread);
-#endif
-  // [0, out_cap): per-binding slots; [out_cap, 2 out_cap): serial results past their slot
-  a.add(&bt->out_idx, std::max<uint64_t>(1, 2 * bt->out_cap));
-  a.add(&bt->out_rep, std::max<uint64_t>(1, 2 * bt->out_cap));
-  a.add(&bt->offsets_d, B + 1);
-  a.add(&bt->off_part, (size_t)(B + kOffChunk - 1) / kOffChunk);
-  a.add(&bt->cidx_d, std::max<uint64_t>(1, 2 * bt->out_cap));
-  a.add(&bt->crep_d, std::max<uint64_t>(1, 2 * bt->out_cap));
-  a.add(&bt->rout, (size_t)std::max(1, nr) * R);
-  a.add(&bt->rstat, std::max(1, nr));
-  a.add(&bt->rsel, (size_t)std::max(1, nr) * R);
-  a.add(&bt->rnsel, std::max(1, nr));
-  a.add(&bt->nhost, 1);
-  a.add(&bt->slow_scratch, bt->slow_slot * bt->slow_grid);
-  if (!bt->l_region_wide.empty()) {
-    a.add(&bt->d_region_wide, bt->l_region_wide.size());
-    a.add(&bt->wide_scratch, bt->wide_slot * bt->wide_grid);
-  }
+  return KP_OK;
+}
+
+// Stage 4: what the estimator classes get. Class orders or not (with_orders), the
+// singleton classes that keep feasible entries only (est_single), the representatives'
+// upload form, and the component-set classes' scratch offsets.
+static void plan_classes(CreateCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  const int B = bt->B ? bt->B : 1;
   // k_select_top (bits mode): class orders, fallback list. k_class_order sorts a class
   // row in LDS (kRedBytes + 8 * nextpow2(C)): a device with less LDS per workgroup
   // keeps the full-candidate kernels instead of failing the launch.
@@ -3426,143 +3366,218 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   // one class per binding (per-binding requests) sorts a Cp row per binding instead,
   // so it keeps the full-candidate kernels (KP_ORDER_AMORT: bindings per class needed)
   const bool orders_pay = (int64_t)bt->crep.size() * order_amort() <= (int64_t)B;
-  // Without them k_select_top thresholds each binding's votes by a histogram instead of
-  // walking an order (kp_top.h), so its fallback list exists either way.
-  if (!bt->crep.empty()) {
-    a.add(&bt->d_fb, std::max(1, bt->n_all_dyn));
-    a.add(&bt->d_ofb, std::max(1, bt->n_all_dyn));
-  }
-  const bool with_orders = s->C <= 16384 && !bt->crep.empty() && orders_pay &&
-                           class_order_lds_bytes(class_order_pad(s->C)) <= e->max_lds;
+  c.with_orders = s->C <= 16384 && !bt->crep.empty() && orders_pay &&
+                  class_order_lds_bytes(class_order_pad(s->C)) <= e->max_lds;
   // singleton classes: feasible entries only, when every reader gathers feasible candidates
   // (no class orders, which sort whole rows; no spread lists; no component-set classes)
   static const bool est_single_on = kp_env_int("KP_EST_SINGLE", 1) != 0;
-  if (est_single_on && !with_orders && bt->crep.size() > 1 && bt->l_cluster.empty() && bt->l_region.empty() &&
+  if (est_single_on && !c.with_orders && bt->crep.size() > 1 && bt->l_cluster.empty() && bt->l_region.empty() &&
       bt->sets_cls.empty()) {
     std::vector<int32_t> cnt(bt->crep.size(), 0);
-    for (uint64_t i = 0; i < n; i++) cnt[(size_t)std::max(0, bt->bcls[i])]++;
+    for (uint64_t i = 0; i < c.n; i++) cnt[(size_t)std::max(0, bt->bcls[i])]++;
     // (a class with a row of the other estimators' answers keeps its whole row: k_est_extra
-    // merges it before ev[5], the feasible-only rows are written after)
+    // merges it before EV_CLASS_ROWS, the feasible-only rows are written after)
     auto has_est = [&](size_t g) { return !bt->cls_est.empty() && bt->cls_est[g] >= 0; };
     for (size_t g = 0; g < bt->crep.size(); g++)
       (g > 0 && cnt[g] == 1 && !has_est(g) ? bt->l_cls_single : bt->l_cls_full).push_back((int32_t)g);
     bt->est_single = !bt->l_cls_single.empty();
-    if (bt->est_single) {
-      a.add(&bt->d_cls_full, bt->l_cls_full.size());
-      a.add(&bt->d_cls_single, bt->l_cls_single.size());
-    }
   }
-  if (with_orders) {
-    a.add(&bt->d_ord, bt->crep.size() * (size_t)s->Cp);
-    a.add(&bt->d_ctot, bt->crep.size());
-    a.add(&bt->d_cok, bt->crep.size());
-    a.add(&bt->d_fbc, std::max<size_t>(1, bt->l_cluster.size()));
-    a.add(&bt->d_fbr, std::max(1, nr));
-    a.add(&bt->d_fba, std::max(1, nr));
-  }
+  // representatives of the k_est_class rows; -1 for the component-set classes (k_sets_rows)
+  c.rep = bt->crep;
+  for (int32_t g : bt->sets_cls) c.rep[g] = -1;
   // component-set classes: per cluster rank its node-run scratch (one run per model
   // node at most, capped at kSetsRunsMax) for k_sets_rows, reused class after class
-  std::vector<int64_t> sets_off;
   if (!bt->sets_cls.empty()) {
-    for (uint64_t i = 0; i < n; i++)
+    for (uint64_t i = 0; i < c.n; i++)
       if (bt->hdr[i].flags & BF_SETS) bt->l_sets.push_back((int32_t)i);
-    sets_off.assign((size_t)s->C + 1, 0);
+    c.sets_off.assign((size_t)s->C + 1, 0);
     // (KP_SETS_RUNS_CAP lowers it: tests of the overflow report)
     const int64_t runs_cap = std::max<int64_t>(1, std::min<int64_t>(kp_env_int("KP_SETS_RUNS_CAP", kSetsRunsMax), kSetsRunsMax));
     for (int r = 0; r < s->C; r++) {
       int64_t nodes = 0;
       for (int g = s->mgrp_off[r]; g < s->mgrp_off[r + 1]; g++) nodes += s->mgrp_cnt[g];
-      sets_off[r + 1] = sets_off[r] + std::max<int64_t>(1, std::min<int64_t>(nodes, runs_cap));
+      c.sets_off[r + 1] = c.sets_off[r] + std::max<int64_t>(1, std::min<int64_t>(nodes, runs_cap));
     }
-    a.add(&bt->d_sets_args, bt->sets_args.size());
-    a.add(&bt->d_sets_off, sets_off.size());
-    a.add(&bt->d_sets_scratch, (size_t)sets_off.back() * (1 + kSetsSlots));
+  }
+}
+
+// Stage 5: every device buffer of the batch registered in one pass (the order fixes the
+// sub-buffer offsets, so it does not change), the arena and the page-locked
+// launch-argument slots.
+static int plan_arena(CreateCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
+  auto pad1 = [](auto& v) {
+    if (v.empty()) v.resize(1);
+  };
+  pad1(bt->ipool);
+  pad1(bt->lpool);
+  pad1(bt->tols);
+  pad1(bt->progs);
+  pad1(bt->instrs);
+  const int B = bt->B ? bt->B : 1;
+  const int nr = (int)bt->l_region.size(), R = std::max(1, s->view.n_regions);
+  const size_t n_cls = bt->crep.size();
+  const uint64_t out2 = std::max<uint64_t>(1, 2 * bt->out_cap);
+  Arena& a = bt->dev;
+  a.pool_dev = e->device;
+  BatchView& v = bt->view;
+  v.B = bt->B;
+  a.add(&v.hdr, bt->hdr.data(), bt->hdr.size(), 1);
+  a.add(&v.ipool, bt->ipool.data(), bt->ipool.size());
+  a.add(&v.lpool, bt->lpool.data(), bt->lpool.size());
+  a.add(&v.tols, bt->tols.data(), bt->tols.size());
+  a.add(&v.progs, bt->progs.data(), bt->progs.size());
+  a.add(&v.instrs, bt->instrs.data(), bt->instrs.size());
+  a.add(&bt->fmask, (size_t)B * s->W);
+  a.add(&bt->d_bcls, bt->bcls.data(), bt->bcls.size(), 1);
+  a.add(&bt->d_crep, c.rep.data(), c.rep.size());
+  a.add(&bt->cls_rows, n_cls * (size_t)s->Cp);
+  a.add(&bt->d_all, bt->l_all.data(), bt->l_all.size(), 1);
+  a.add(&bt->d_all_cls, bt->l_all_cls.data(), bt->l_all_cls.size(), 1);
+  a.add(&bt->d_cluster, bt->l_cluster.data(), bt->l_cluster.size(), 1);
+  a.add(&bt->d_region, bt->l_region.data(), bt->l_region.size(), 1);
+  a.add(&bt->d_slowlist, std::max<size_t>(1, bt->l_slow.size()));  // (appended on the device)
+  a.add(&bt->d_cs, bt->l_cs.data(), bt->l_cs.size(), 1);
+  a.add(&bt->status, B);
+  a.add(&bt->errc, B);
+  a.add(&bt->slow, B);
+  a.add(&bt->arg, B);
+  a.add(&bt->start, B);
+  a.add(&bt->count, B);
+  a.add(&bt->counter, 1);
+  a.add(&bt->stats, kStatSlots);
+  a.add(&bt->d_kargs, kArgSlots);
+#if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
+  a.add(&bt->dbg, kDbgSlots * kDbgSpread);
+#endif
+  // [0, out_cap): per-binding slots; [out_cap, 2 out_cap): serial results past their slot
+  a.add(&bt->out_idx, out2);
+  a.add(&bt->out_rep, out2);
+  a.add(&bt->offsets_d, B + 1);
+  a.add(&bt->off_part, (size_t)(B + kOffChunk - 1) / kOffChunk);
+  a.add(&bt->cidx_d, out2);
+  a.add(&bt->crep_d, out2);
+  a.add(&bt->rout, (size_t)std::max(1, nr) * R);
+  a.add(&bt->rstat, std::max(1, nr));
+  a.add(&bt->rsel, (size_t)std::max(1, nr) * R);
+  a.add(&bt->rnsel, std::max(1, nr));
+  a.add(&bt->nhost, 1);
+  a.add(&bt->slow_scratch, bt->slow_slot * bt->slow_grid);
+  if (!bt->l_region_wide.empty()) {
+    a.add(&bt->d_region_wide, bt->l_region_wide.data(), bt->l_region_wide.size());
+    a.add(&bt->wide_scratch, bt->wide_slot * bt->wide_grid);
+  }
+  // Without class orders k_select_top thresholds each binding's votes by a histogram instead
+  // of walking an order (kp_top.h), so its fallback list exists either way.
+  if (n_cls) {
+    a.add(&bt->d_fb, std::max(1, bt->n_all_dyn));
+    a.add(&bt->d_ofb, std::max(1, bt->n_all_dyn));
+  }
+  if (bt->est_single) {
+    a.add(&bt->d_cls_full, bt->l_cls_full.data(), bt->l_cls_full.size());
+    a.add(&bt->d_cls_single, bt->l_cls_single.data(), bt->l_cls_single.size());
+  }
+  if (c.with_orders) {
+    a.add(&bt->d_ord, n_cls * (size_t)s->Cp);
+    a.add(&bt->d_ctot, n_cls);
+    a.add(&bt->d_cok, n_cls);
+    a.add(&bt->d_fbc, std::max<size_t>(1, bt->l_cluster.size()));
+    a.add(&bt->d_fbr, std::max(1, nr));
+    a.add(&bt->d_fba, std::max(1, nr));
+  }
+  if (!bt->sets_cls.empty()) {
+    a.add(&bt->d_sets_args, bt->sets_args.data(), bt->sets_args.size());
+    a.add(&bt->d_sets_off, c.sets_off.data(), c.sets_off.size());
+    a.add(&bt->d_sets_scratch, (size_t)c.sets_off.back() * (1 + kSetsSlots));
     a.add(&bt->d_sets_ovf, bt->sets_cls.size());
-    a.add(&bt->d_sets_list, bt->l_sets.size());
+    a.add(&bt->d_sets_list, bt->l_sets.data(), bt->l_sets.size());
   }
   if (!bt->l_est_cls.empty()) {
-    a.add(&bt->d_cls_est, bt->cls_est.size());
-    a.add(&bt->d_est_cls, bt->l_est_cls.size());
-    a.add(&bt->d_est_rows, est_rows.size());
+    a.add(&bt->d_cls_est, bt->cls_est.data(), bt->cls_est.size());
+    a.add(&bt->d_est_cls, bt->l_est_cls.data(), bt->l_est_cls.size());
+    a.add(&bt->d_est_rows, c.est_rows.data(), c.est_rows.size());
   }
   if (!bt->l_flt.empty()) {
-    a.add(&bt->d_flt_list, bt->l_flt.size());
-    a.add(&bt->d_flt_rows, flt_rows.size());
+    a.add(&bt->d_flt_list, bt->l_flt.data(), bt->l_flt.size());
+    a.add(&bt->d_flt_rows, c.flt_rows.data(), c.flt_rows.size());
   }
-  const auto tp1 = std::chrono::steady_clock::now();
+  c.tp1 = std::chrono::steady_clock::now();
   HIPCHK(a.alloc());
   bt->h_kargs = (KArgs*)pinned_get(sizeof(KArgs) * kArgSlots, &bt->h_kargs_bytes);
   if (!bt->h_kargs) {
     e->err = "kp_batch_create: page-locked launch-argument slots";
     return KP_EDEVICE;
   }
-  bt->create_stream = e->stream;  // (an early return below waits for the uploads queued so far)
-  const auto tp2 = std::chrono::steady_clock::now();
-  auto up = [&](void* d, const void* h, size_t bytes) {
-    return dev::h2d(d, h, bytes, e->stream);
-  };
-  HIPCHK(up(d_hdr, bt->hdr.data(), sizeof(BindHdr) * bt->hdr.size()));
-  HIPCHK(up(d_ipool, bt->ipool.data(), 4 * bt->ipool.size()));
-  HIPCHK(up(d_lpool, bt->lpool.data(), 8 * bt->lpool.size()));
-  HIPCHK(up(d_tols, bt->tols.data(), sizeof(Tol) * bt->tols.size()));
-  HIPCHK(up(d_progs, bt->progs.data(), sizeof(Prog) * bt->progs.size()));
-  HIPCHK(up(d_instrs, bt->instrs.data(), sizeof(Instr) * bt->instrs.size()));
-  HIPCHK(up(bt->d_bcls, bt->bcls.data(), 4 * bt->bcls.size()));
-  {  // representatives of the k_est_class rows; -1 for the component-set classes (k_sets_rows)
-    std::vector<int32_t> rep = bt->crep;
-    for (int32_t g : bt->sets_cls) rep[g] = -1;
-    HIPCHK(up(bt->d_crep, rep.data(), 4 * rep.size()));
-  }
-  if (!bt->sets_cls.empty()) {
-    HIPCHK(up(bt->d_sets_args, bt->sets_args.data(), sizeof(SetsArgs) * bt->sets_args.size()));
-    HIPCHK(up(bt->d_sets_off, sets_off.data(), 8 * sets_off.size()));
-    HIPCHK(up(bt->d_sets_list, bt->l_sets.data(), 4 * bt->l_sets.size()));
-  }
-  if (bt->est_single) {
-    HIPCHK(up(bt->d_cls_full, bt->l_cls_full.data(), 4 * bt->l_cls_full.size()));
-    HIPCHK(up(bt->d_cls_single, bt->l_cls_single.data(), 4 * bt->l_cls_single.size()));
-  }
-  if (!bt->l_est_cls.empty()) {
-    HIPCHK(up(bt->d_cls_est, bt->cls_est.data(), 4 * bt->cls_est.size()));
-    HIPCHK(up(bt->d_est_cls, bt->l_est_cls.data(), 4 * bt->l_est_cls.size()));
-    HIPCHK(up(bt->d_est_rows, est_rows.data(), 4 * est_rows.size()));
-    if (kp_env_flag("KP_PACK_TIMING"))
-      fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
-              bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + est_rows.size()));
-  }
-  if (!bt->l_flt.empty()) {
-    HIPCHK(up(bt->d_flt_list, bt->l_flt.data(), sizeof(FltPair) * bt->l_flt.size()));
-    HIPCHK(up(bt->d_flt_rows, flt_rows.data(), 8 * flt_rows.size()));
-    if (kp_env_flag("KP_PACK_TIMING"))
-      fprintf(stderr, "kp_batch_create_filters: %zu bindings with a row, %zu bytes uploaded for them\n",
-              bt->l_flt.size(), sizeof(FltPair) * bt->l_flt.size() + 8 * flt_rows.size());
-  }
-  HIPCHK(up(bt->d_all, bt->l_all.data(), 4 * bt->l_all.size()));
-  bt->l_all_cls.resize(bt->l_all.size());
-  for (size_t i = 0; i < bt->l_all.size(); i++) bt->l_all_cls[i] = bt->bcls[bt->l_all[i]];
-  HIPCHK(up(bt->d_all_cls, bt->l_all_cls.data(), 4 * bt->l_all_cls.size()));
-  HIPCHK(up(bt->d_cluster, bt->l_cluster.data(), 4 * bt->l_cluster.size()));
-  HIPCHK(up(bt->d_region, bt->l_region.data(), 4 * bt->l_region.size()));
-  if (!bt->l_region_wide.empty())
-    HIPCHK(up(bt->d_region_wide, bt->l_region_wide.data(), 4 * bt->l_region_wide.size()));
-  HIPCHK(up(bt->d_cs, bt->l_cs.data(), 4 * bt->l_cs.size()));
+  return KP_OK;
+}
+
+// Stage 6: the copies, k_slow's flags cleared, the sync, and the KP_PACK_TIMING lines.
+// create_stream is set while copies may be queued: an early return waits for them in
+// ~kp_batch before the arena goes back to the pool.
+static int upload(CreateCtx& c) {
+  kp_engine* e = c.e;
+  kp_batch* bt = c.bt;
+  const int B = bt->B ? bt->B : 1;
+  bt->create_stream = e->stream;
+  c.tp2 = std::chrono::steady_clock::now();
+  HIPCHK(bt->dev.upload(e->stream));
   HIPCHK(dev::fill(bt->slow, 0, 4 * (size_t)B, e->stream));
   HIPCHK(dev::sync(e->stream));
   if (kp_env_flag("KP_PACK_TIMING")) {
+    if (!bt->l_est_cls.empty())
+      fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
+              bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + c.est_rows.size()));
+    if (!bt->l_flt.empty())
+      fprintf(stderr, "kp_batch_create_filters: %zu bindings with a row, %zu bytes uploaded for them\n",
+              bt->l_flt.size(), sizeof(FltPair) * bt->l_flt.size() + 8 * c.flt_rows.size());
     const auto tp3 = std::chrono::steady_clock::now();
     auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    fprintf(stderr, "kp_batch_create: pack %.1f ms, alloc %.1f ms, upload %.1f ms\n", ms(tp0, tp1), ms(tp1, tp2),
-            ms(tp2, tp3));
+    fprintf(stderr, "kp_batch_create: pack %.1f ms, alloc %.1f ms, upload %.1f ms\n", ms(c.tp0, c.tp1),
+            ms(c.tp1, c.tp2), ms(c.tp2, tp3));
   }
-  BatchView& v = bt->view;
-  v.B = bt->B;
-  v.hdr = d_hdr;
-  v.ipool = d_ipool;
-  v.lpool = d_lpool;
-  v.tols = d_tols;
-  v.progs = d_progs;
-  v.instrs = d_instrs;
   bt->create_stream = nullptr;
+  return KP_OK;
+}
+
+// The validations come in this order, which decides the error a call wrong in two ways
+// sees: estimates, filters, the components check, then the packer.
+static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
+                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
+                             const kp_estimates* est, const kp_filter_answers* flt) {
+  if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
+  if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
+  (void)dev::set_device(e->device);
+  CreateCtx c{e, const_cast<kp_snapshot*>(sc), bindings, n, est, flt};
+  kp_snapshot* s = c.s;
+  if (int rc = take_estimates(c)) return rc;
+  if (int rc = take_filters(c)) return rc;
+  auto* bt = new kp_batch();
+  std::unique_ptr<kp_batch> guard(bt);
+  c.bt = bt;
+  bt->snap = s;
+  bt->B = (int)n;
+  bt->hdr.resize(n);
+  bt->flt_plugins = c.flt_plugins;
+  bt->l_flt = std::move(c.flt_list);
+  c.tp0 = std::chrono::steady_clock::now();
+  if (s->opts.multiple_pod_templates_scheduling)
+    for (uint64_t i = 0; i < n; i++)
+      if (bindings[i].n_components > 0 && !bindings[i].components) {
+        e->err = "kp_batch_create: binding " + std::to_string(i) +
+                 " has n_components > 0 but no components (the MultiplePodTemplatesScheduling gate reads them)";
+        return KP_EINVAL;
+      }
+  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache, c.est ? c.est->row_of : nullptr)) {
+    e->err = bt->err.empty() ? "batch pools exceed 2^31 entries" : bt->err;
+    return KP_ENOTSUP;
+  }
+  if (int rc = route_lists(c)) return rc;
+  if (int rc = size_serial(c)) return rc;
+  plan_classes(c);
+  if (int rc = plan_arena(c)) return rc;
+  if (int rc = upload(c)) return rc;
   *out = guard.release();
   return KP_OK;
 }
@@ -3829,7 +3844,7 @@ struct SubmitCtx {
 
 // Stage 1, stream2: every row the selections read. The estimator classes' rows, the
 // component-set classes' rows, the other estimators' answers, k_filter and the out-of-tree
-// verdicts (or the pair kernel's per-binding rows instead), then the class orders; ev[4]
+// verdicts (or the pair kernel's per-binding rows instead), then the class orders; EV_ROWS_END
 // marks them complete, and stream waits for it.
 static int submit_rows(SubmitCtx& c) {
   kp_engine* e = c.e;
@@ -3838,7 +3853,7 @@ static int submit_rows(SubmitCtx& c) {
   const int B = bt->B, fast = c.fast;
   const bool bits = c.bits;
   dev::stream_t st = e->stream, sp = e->stream2;
-  HIPCHK(dev::event_record(e->ev[3], sp));
+  HIPCHK(dev::event_record(e->ev[EV_ROWS_BEGIN], sp));
   // component-set classes (BF_SETS bindings): their class rows (after the estimator
   // classes' rows, before k_class_order reads them all), and in the pair-row mode those
   // bindings' own rows rebuilt from them (feasible clusters only)
@@ -3861,10 +3876,10 @@ static int submit_rows(SubmitCtx& c) {
       KPROF(sp, "k_est_extra", bt->l_est_cls.size(), -1,
             dev::est_extra(sp, s->Cp, bt->d_est_cls, (int)bt->l_est_cls.size(), nullptr, bt->d_cls_est, bt->d_est_rows,
                            bt->cls_rows));
-    HIPCHK(dev::event_record(e->ev[5], sp));  // every class row is written (k_class_order's input)
+    HIPCHK(dev::event_record(e->ev[EV_CLASS_ROWS], sp));  // every class row is written (k_class_order's input)
     KPROF(sp, "k_filter", B, -1, dev::filter(sp, s->view, bt->view, bt->fmask));
     // the out-of-tree filter verdicts ANDed into their bindings' rows, ahead of every reader
-    // of the feasibility rows (the feasible-only class rows next, then all behind ev[4])
+    // of the feasibility rows (the feasible-only class rows next, then all behind EV_ROWS_END)
     if (!bt->l_flt.empty())
       KPROF(sp, "k_filter_extra", bt->l_flt.size(), -1,
             dev::filter_extra(sp, s->view, bt->d_flt_list, (int)bt->l_flt.size(), bt->d_flt_rows, bt->fmask, nullptr));
@@ -3900,23 +3915,23 @@ static int submit_rows(SubmitCtx& c) {
     // k_filter and stream2 waits for it (profiled runs keep it on stream2: each kernel's
     // event time is then its own)
     dev::stream_t so = e->prof ? sp : e->stream3;
-    if (so != sp) HIPCHK(dev::stream_wait(so, e->ev[5]));
+    if (so != sp) HIPCHK(dev::stream_wait(so, e->ev[EV_CLASS_ROWS]));
     KPROF(so, "k_class_order", bt->crep.size(), -1,
           dev::class_order(so, s->view, bt->cls_rows, (int)bt->crep.size(), bt->d_ord, bt->d_ctot, bt->d_cok));
     if (so != sp) {
-      HIPCHK(dev::event_record(e->ev[6], so));
-      HIPCHK(dev::stream_wait(sp, e->ev[6]));
+      HIPCHK(dev::event_record(e->ev[EV_CLASS_ORDER], so));
+      HIPCHK(dev::stream_wait(sp, e->ev[EV_CLASS_ORDER]));
     }
   }
-  HIPCHK(dev::event_record(e->ev[4], sp));
-  HIPCHK(dev::stream_wait(st, e->ev[4]));  // every pair row precedes the rest
-  HIPCHK(dev::event_record(e->ev[1], st));
+  HIPCHK(dev::event_record(e->ev[EV_ROWS_END], sp));
+  HIPCHK(dev::stream_wait(st, e->ev[EV_ROWS_END]));  // every pair row precedes the rest
+  HIPCHK(dev::event_record(e->ev[EV_SELECT_BEGIN], st));
   return KP_OK;
 }
 
 // Stage 2, stream2: the SEL_ALL bindings. k_select_top's slices over [0, n_all_dyn) and
 // the full-candidate kernel over what they hand back, k_select_static, the streamed kernel
-// over the rest. ev[7] -> ev[8] times it.
+// over the rest. EV_SEL_ALL_BEGIN -> EV_SEL_ALL_END times it.
 static int submit_sel_all(SubmitCtx& c) {
   kp_engine* e = c.e;
   kp_batch* bt = c.bt;
@@ -3924,7 +3939,7 @@ static int submit_sel_all(SubmitCtx& c) {
   const bool bits = c.bits, top = c.top;
   const int cap = c.cap;
   dev::stream_t sp = e->stream2;
-  HIPCHK(dev::event_record(e->ev[7], sp));
+  HIPCHK(dev::event_record(e->ev[EV_SEL_ALL_BEGIN], sp));
   if (!bt->l_all.empty()) {
     KArgs k = c.ka;
     k.list = bt->d_all;
@@ -3940,7 +3955,7 @@ static int submit_sel_all(SubmitCtx& c) {
       // k_select_top over [0, n_all_dyn), small slices for [0, n_top_small); the
       // bindings it hands back (other strategies, subsets past capacity, ...) run with
       // every candidate from its fallback list
-      HIPCHK(dev::event_record(e->ev[12], sp));
+      HIPCHK(dev::event_record(e->ev[EV_TOP_BEGIN], sp));
       // the two slices' launches run concurrently, the large one on stream3 (which the
       // cluster-spread kernels use after it), so neither drains the CUs alone
       // (profiled steps keep both on one stream: each launch's HIP-event time is then its own)
@@ -3957,45 +3972,46 @@ static int submit_sel_all(SubmitCtx& c) {
         g.lcls = bt->d_all_cls + (part == 0 ? 0 : bt->n_top_small);
         g.n = part == 0 ? bt->n_top_small : bt->n_all_dyn - bt->n_top_small;
         if (g.n <= 0) continue;
-        TopArgs ta{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + 9, cap_p};
+        TopArgs ta{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + KS_TOP_FALLBACK, cap_p};
         if (part == 1 && mid) {
           ta.ofb = bt->d_ofb;
-          ta.ofb_n = bt->stats + 16;
+          ta.ofb_n = bt->stats + KS_TOP_OVERFLOW;
         }
         const size_t slice = (top_lds_bytes(s->Cp, cap_p) + 15) & ~(size_t)15;
         dev::stream_t sx_ = split && part == 1 ? e->stream3 : sp;
-        if (split && part == 1) HIPCHK(dev::stream_wait(sx_, e->ev[4]));
+        if (split && part == 1) HIPCHK(dev::stream_wait(sx_, e->ev[EV_ROWS_END]));
         KPROF(sx_, "k_select_top", g.n, -1, dev::select_top(sx_, g, ta, slice));
         if (part == 1 && mid) {
           KArgs o = k;
           o.list = bt->d_ofb;
-          o.n = g.n;  // (the list's capacity; its length is stats[16])
-          o.n_dev = bt->stats + 16;
-          TopArgs tb{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + 9, c.top_cap};
+          o.n = g.n;  // (the list's capacity; its length is stats[KS_TOP_OVERFLOW])
+          o.n_dev = bt->stats + KS_TOP_OVERFLOW;
+          TopArgs tb{bt->d_ord, bt->d_ctot, bt->d_cok, bt->d_fb, bt->stats + KS_TOP_FALLBACK, c.top_cap};
           const size_t slice_l = (top_lds_bytes(s->Cp, c.top_cap) + 15) & ~(size_t)15;
           // (units 0: the launch re-runs bindings the kernel's units already count)
           KPROF(sx_, "k_select_top", 0, -1, dev::select_top(sx_, o, tb, slice_l, kTopOverGrid));
         }
         if (split && part == 1) {
-          HIPCHK(dev::event_record(e->ev[10], sx_));
-          HIPCHK(dev::stream_wait(sp, e->ev[10]));  // both slices' fallbacks precede k_select_all
+          HIPCHK(dev::event_record(e->ev[EV_TOP_LARGE], sx_));
+          HIPCHK(dev::stream_wait(sp, e->ev[EV_TOP_LARGE]));  // both slices' fallbacks precede k_select_all
         }
       }
-      HIPCHK(dev::event_record(e->ev[13], sp));
+      HIPCHK(dev::event_record(e->ev[EV_TOP_END], sp));
       KArgs f = k;
       f.list = bt->d_fb;
       f.n = bt->n_all_dyn;
-      f.n_dev = bt->stats + 9;
+      f.n_dev = bt->stats + KS_TOP_FALLBACK;
       if (c.gate) {
         c.f_def = f;
         c.defer_all = true;
         c.defer_all_stream = stream_all;
       } else if (stream_all) {
         const SelectExtra sxa1 = c.with_args(f, sp);  // (the slot is copied before the launch is timed)
-        KPROF(sp, "k_select_all_stream", 0, 9,
+        KPROF(sp, "k_select_all_stream", 0, KS_TOP_FALLBACK,
               dev::select(sp, SEL_LAUNCH_ALL_STREAM, f, sel_stream_lds_bytes(s->Cp), cap, sxa1));
       } else {
-        KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), 0, 9, dev::select(sp, SEL_LAUNCH_ALL, f, smem_all(s), cap, c.sx));
+        KPROF(sp, sel_name(SEL_LAUNCH_ALL, smem_all(s)), 0, KS_TOP_FALLBACK,
+              dev::select(sp, SEL_LAUNCH_ALL, f, smem_all(s), cap, c.sx));
       }
     } else if (na > 0) {
       KArgs g = k;
@@ -4023,44 +4039,44 @@ static int submit_sel_all(SubmitCtx& c) {
             dev::select(sp, SEL_LAUNCH_ALL_STREAM, g, sel_stream_lds_bytes(s->Cp), cap, sxa2));
     }
   }
-  HIPCHK(dev::event_record(e->ev[8], sp));  // k_select_all alone: ev[7] -> ev[8]
+  HIPCHK(dev::event_record(e->ev[EV_SEL_ALL_END], sp));  // k_select_all alone: EV_SEL_ALL_BEGIN -> EV_SEL_ALL_END
   return KP_OK;
 }
 
-// Stage 3, stream3 (behind the rows, ev[4]): the cluster-spread bindings, over the class
-// orders first where the batch has them. ev[14] -> ev[15] times it.
+// Stage 3, stream3 (behind the rows, EV_ROWS_END): the cluster-spread bindings, over the class
+// orders first where the batch has them. EV_CLUSTER_BEGIN -> EV_CLUSTER_END times it.
 static int submit_cluster_spread(SubmitCtx& c) {
   kp_engine* e = c.e;
   kp_batch* bt = c.bt;
   kp_snapshot* s = c.s;
   const int cap = c.cap;
   dev::stream_t s3 = e->stream3;
-  HIPCHK(dev::stream_wait(s3, e->ev[4]));
+  HIPCHK(dev::stream_wait(s3, e->ev[EV_ROWS_END]));
   if (bt->l_cluster.empty()) return KP_OK;
   KArgs k = c.ka;
   k.list = bt->d_cluster;
   k.n = (int)bt->l_cluster.size();
-  HIPCHK(dev::event_record(e->ev[14], s3));
+  HIPCHK(dev::event_record(e->ev[EV_CLUSTER_BEGIN], s3));
   if (c.spread_orders) {
     // the class-order selection, one wave per binding; what it hands back runs below
     k.ord = bt->d_ord;
     k.cok = bt->d_cok;
-    k.n_order = bt->stats + 10;
-    OrderArgs oa{nullptr, nullptr, nullptr, bt->d_fbc, bt->stats + 12, 0};
+    k.n_order = bt->stats + KS_CLUSTER_ORDER;
+    OrderArgs oa{nullptr, nullptr, nullptr, bt->d_fbc, bt->stats + KS_FB_CLUSTER, 0};
     KPROF(s3, "k_spread_order", k.n, -1,
           dev::spread_order(s3, k, oa, (order_lds_bytes(s->view.W, s->view.n_regions) + 15) & ~(size_t)15));
     k.sub = bt->d_fbc;
-    k.n_dev = bt->stats + 12;
+    k.n_dev = bt->stats + KS_FB_CLUSTER;
   }
   if (c.gate && k.n_dev) {
     c.cl_def = k;
     c.defer_cl = true;
   } else {  // (the argument slot is copied before the launch is timed)
     const SelectExtra sxa3 = c.with_args(k, s3);
-    KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 12 : -1,
+    KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? KS_FB_CLUSTER : -1,
           dev::select(s3, SEL_LAUNCH_CLUSTER, k, smem_cluster(s, cap), cap, sxa3));
   }
-  HIPCHK(dev::event_record(e->ev[15], s3));
+  HIPCHK(dev::event_record(e->ev[EV_CLUSTER_END], s3));
   return KP_OK;
 }
 
@@ -4082,23 +4098,24 @@ static int submit_region_chain(SubmitCtx& c) {
   if (c.spread_orders) {  // region_b_by_order
     k.ord = bt->d_ord;
     k.cok = bt->d_cok;
-    k.n_order = bt->stats + 11;
+    k.n_order = bt->stats + KS_REGION_ORDER;
   }
   if (c.spread_orders) {  // stage A of the order-eligible bindings, one wave each; the rest below
     KArgs ko = k;
     ko.n_order = nullptr;
-    KPROF(st, "k_region_a_order", ko.n, -1, dev::region_a_order(st, ko, bt->rout, bt->rstat, bt->d_fba, bt->stats + 14,
-                               (region_a_order_lds_bytes(R, s->view.W) + 15) & ~(size_t)15));
+    KPROF(st, "k_region_a_order", ko.n, -1,
+          dev::region_a_order(st, ko, bt->rout, bt->rstat, bt->d_fba, bt->stats + KS_FB_REGION_A,
+                              (region_a_order_lds_bytes(R, s->view.W) + 15) & ~(size_t)15));
     KArgs kf = k;
     kf.sub = bt->d_fba;
-    kf.n_dev = bt->stats + 14;
+    kf.n_dev = bt->stats + KS_FB_REGION_A;
     uint32_t nfa = 0;
-    HIPCHK(dev::d2h(&nfa, bt->stats + 14, 4, st));
+    HIPCHK(dev::d2h(&nfa, bt->stats + KS_FB_REGION_A, 4, st));
     HIPCHK(dev::sync(st));
     if (nfa > 0) {  // (the argument slot is copied before the launch is timed)
       SelectExtra sxa4 = c.with_args(kf, st);
       sxa4.list_grid = (int)nfa;
-      KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), 0, 14,
+      KPROF(st, sel_name(SEL_LAUNCH_REGION_A, smem_region_a(s)), 0, KS_FB_REGION_A,
             dev::select(st, SEL_LAUNCH_REGION_A, kf, smem_region_a(s), cap, sxa4));
     }
   } else {  // (the argument slot is copied before the launch is timed)
@@ -4163,17 +4180,17 @@ static int submit_region_chain(SubmitCtx& c) {
   }
   uint32_t nfb = 1;
   if (c.spread_orders) {
-    OrderArgs oa{bt->rout, bt->rsel, bt->rnsel, bt->d_fbr, bt->stats + 13, 1};
+    OrderArgs oa{bt->rout, bt->rsel, bt->rnsel, bt->d_fbr, bt->stats + KS_FB_REGION, 1};
     KPROF(st, "k_spread_order", k.n, -1, dev::spread_order(st, k, oa, (order_lds_bytes(s->view.W, R) + 15) & ~(size_t)15));
     k.sub = bt->d_fbr;
-    k.n_dev = bt->stats + 13;
-    HIPCHK(dev::d2h(&nfb, bt->stats + 13, 4, st));
+    k.n_dev = bt->stats + KS_FB_REGION;
+    HIPCHK(dev::d2h(&nfb, bt->stats + KS_FB_REGION, 4, st));
     HIPCHK(dev::sync(st));
   }
   if (nfb > 0) {  // (the argument slot is copied before the launch is timed)
     SelectExtra sxa6 = c.with_args(k, st);
     if (k.n_dev) sxa6.list_grid = (int)nfb;
-    KPROF(st, sel_name(SEL_LAUNCH_REGION_B, smem_region_b(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? 13 : -1,
+    KPROF(st, sel_name(SEL_LAUNCH_REGION_B, smem_region_b(s, cap)), k.n_dev ? 0 : k.n, k.n_dev ? KS_FB_REGION : -1,
           dev::select(st, SEL_LAUNCH_REGION_B, k, smem_region_b(s, cap), cap, sxa6));
   }
   // the selections past k_region_b's lists (marked there in a.slow), queued behind it: no
@@ -4183,9 +4200,9 @@ static int submit_region_chain(SubmitCtx& c) {
     kw.list = bt->d_region;
     kw.n = nr;
     const SelectExtra sxw = c.with_args(kw, st);
-    KPROF(st, "k_region_wide", 0, 17,
+    KPROF(st, "k_region_wide", 0, KS_REGION_WIDE_DONE,
           dev::region_wide(st, kw, sxw, bt->d_region_wide, (int)bt->l_region_wide.size(), bt->wide_scratch,
-                           bt->wide_slot, bt->wide_grid, bt->slow_cap, bt->wide_sort, bt->stats + 17));
+                           bt->wide_slot, bt->wide_grid, bt->slow_cap, bt->wide_sort, bt->stats + KS_REGION_WIDE_DONE));
   }
   return KP_OK;
 }
@@ -4204,34 +4221,34 @@ static int submit_slow(SubmitCtx& c) {
   kp_snapshot* s = c.s;
   const int cap = c.cap;
   dev::stream_t s3 = e->stream3;
-  HIPCHK(dev::stream_wait(s3, e->ev[8]));
+  HIPCHK(dev::stream_wait(s3, e->ev[EV_SEL_ALL_END]));
   uint32_t nslow = (uint32_t)bt->slow_grid;
   if (c.gate) {
-    uint32_t hs[16];  // (stats [0] flagged, [9] SEL_ALL fallbacks, [12] cluster-spread fallbacks)
+    uint32_t hs[KS_CHECK + 1];  // (KS_SLOW_TOTAL flagged, KS_TOP_FALLBACK / KS_FB_CLUSTER fallbacks among them)
     HIPCHK(dev::d2h(hs, bt->stats, sizeof(hs), s3));
     HIPCHK(dev::sync(s3));
-    nslow = hs[0];
+    nslow = hs[KS_SLOW_TOTAL];
     bool more = false;  // a deferred fallback runs: it may flag bindings for k_slow
-    if (c.defer_all && hs[9] > 0) {
+    if (c.defer_all && hs[KS_TOP_FALLBACK] > 0) {
       const KArgs& f = c.f_def;
       if (c.defer_all_stream) {
         SelectExtra sxa1 = c.with_args(f, s3);
-        sxa1.list_grid = (int)hs[9];
-        KPROF(s3, "k_select_all_stream", hs[9], -1,
+        sxa1.list_grid = (int)hs[KS_TOP_FALLBACK];
+        KPROF(s3, "k_select_all_stream", hs[KS_TOP_FALLBACK], -1,
               dev::select(s3, SEL_LAUNCH_ALL_STREAM, f, sel_stream_lds_bytes(s->Cp), cap, sxa1));
       } else {
         SelectExtra sxg = c.sx;
-        sxg.list_grid = (int)hs[9];
-        KPROF(s3, sel_name(SEL_LAUNCH_ALL, smem_all(s)), hs[9], -1,
+        sxg.list_grid = (int)hs[KS_TOP_FALLBACK];
+        KPROF(s3, sel_name(SEL_LAUNCH_ALL, smem_all(s)), hs[KS_TOP_FALLBACK], -1,
               dev::select(s3, SEL_LAUNCH_ALL, f, smem_all(s), cap, sxg));
       }
       more = true;
     }
-    if (c.defer_cl && hs[12] > 0) {
+    if (c.defer_cl && hs[KS_FB_CLUSTER] > 0) {
       const KArgs& k = c.cl_def;
       SelectExtra sxa3 = c.with_args(k, s3);
-      sxa3.list_grid = (int)hs[12];
-      KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), hs[12], -1,
+      sxa3.list_grid = (int)hs[KS_FB_CLUSTER];
+      KPROF(s3, sel_name(SEL_LAUNCH_CLUSTER, smem_cluster(s, cap)), hs[KS_FB_CLUSTER], -1,
             dev::select(s3, SEL_LAUNCH_CLUSTER, k, smem_cluster(s, cap), cap, sxa3));
       more = true;
     }
@@ -4246,12 +4263,12 @@ static int submit_slow(SubmitCtx& c) {
     if (!e->slow_order) k.ord = nullptr;
     SelectExtra sxs = c.with_args(k, s3);
     sxs.grid = (int)std::min<uint32_t>((uint32_t)bt->slow_grid, nslow);
-    KPROF(s3, "k_slow", 0, 0,
+    KPROF(s3, "k_slow", 0, KS_SLOW_TOTAL,
           dev::select(s3, SEL_LAUNCH_SLOW, k,
                       slow_lds_bytes(s->Cp, c.sx.lds_area, c.sx.lds_sort),
                       bt->slow_cap, sxs));
   }
-  HIPCHK(dev::event_record(e->ev[9], s3));
+  HIPCHK(dev::event_record(e->ev[EV_SLOW_END], s3));
   return KP_OK;
 }
 
@@ -4266,9 +4283,9 @@ static int submit_results(SubmitCtx& c) {
   kp_snapshot* s = c.s;
   const int B = bt->B;
   dev::stream_t st = e->stream;
-  HIPCHK(dev::stream_wait(st, e->ev[8]));
-  HIPCHK(dev::stream_wait(st, e->ev[9]));  // k_slow (stream3) and every select kernel precede the results
-  HIPCHK(dev::event_record(e->ev[2], st));
+  HIPCHK(dev::stream_wait(st, e->ev[EV_SEL_ALL_END]));
+  HIPCHK(dev::stream_wait(st, e->ev[EV_SLOW_END]));  // k_slow (stream3) and every select kernel precede the results
+  HIPCHK(dev::event_record(e->ev[EV_SELECT_END], st));
   KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->count, B, bt->offsets_d, bt->off_part));
   if (c.packed) {
     KPROF(st, "k_pack", B, -1,
@@ -4301,7 +4318,7 @@ static int submit_results(SubmitCtx& c) {
   return KP_OK;
 }
 
-static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
+static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
   if (!e || !bt) return KP_EINVAL;
   if (int rc = refuse_out_of_tree(e, bt->snap, bt->flt_plugins)) return rc;
   (void)dev::set_device(e->device);
@@ -4339,8 +4356,8 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
 #if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
   HIPCHK(dev::fill(bt->dbg, 0, kDbgSlots * kDbgSpread * 8, st));
 #endif
-  HIPCHK(dev::event_record(e->ev[0], st));
-  HIPCHK(dev::stream_wait(e->stream2, e->ev[0]));  // the fills above precede every kernel
+  HIPCHK(dev::event_record(e->ev[EV_FILLS], st));
+  HIPCHK(dev::stream_wait(e->stream2, e->ev[EV_FILLS]));  // the fills above precede every kernel
   SubmitCtx c(e, bt, packed);
   if (!c.bits) {
     if (ensure_rows(e, bt)) return KP_EDEVICE;
@@ -4367,7 +4384,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed = false) {
 
 // Exactly one of out / pout is given: the format the caller collects in, which must be
 // the one the call was submitted in.
-static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout = nullptr) {
+static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout) {
   if (!e || !bt || (!out && !pout)) return KP_EINVAL;
   SchedPend& pd = bt->pend;
   if (!pd.live) {
@@ -4388,13 +4405,8 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     bt->h_offsets.assign(1, 0);
     bt->h_status.clear();
     bt->sched_done = true;
-    if (packed) {
-      memset(pout, 0, sizeof(*pout));
-      pout->offsets = bt->h_offsets.data();
-    } else {
-      memset(out, 0, sizeof(*out));
-      out->offsets = bt->h_offsets.data();
-    }
+    auto none = [&](auto* r) { memset(r, 0, sizeof(*r)), r->offsets = bt->h_offsets.data(); };
+    packed ? none(pout) : none(out);
     return KP_OK;
   }
   dev::stream_t st = e->stream;
@@ -4481,28 +4493,28 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   // (the engine's events time this call unless a later submit has re-recorded them)
   const bool timed = pd.seq == e->submit_seq;
   auto ems = [&](int a, int b) { return timed ? dev::event_ms(e->ev[a], e->ev[b]) : 0.f; };
-  const float ms_pair = ems(3, 4);
-  const float ms_filter = bits ? ems(5, 4) : 0.f;
-  const float ms_sel = ems(1, 2);
+  const float ms_pair = ems(EV_ROWS_BEGIN, EV_ROWS_END);
+  const float ms_filter = bits ? ems(EV_CLASS_ROWS, EV_ROWS_END) : 0.f;
+  const float ms_sel = ems(EV_SELECT_BEGIN, EV_SELECT_END);
   tm.pair_launches = bits ? 2 : 1;
   tm.pair_kind = (uint32_t)fast;
   tm.pair_kernel_ms = ms_pair;
   tm.select_kernel_ms = ms_sel;
   tm.filter_kernel_ms = ms_filter;
-  tm.sel_all_kernel_ms = ems(7, 8);
+  tm.sel_all_kernel_ms = ems(EV_SEL_ALL_BEGIN, EV_SEL_ALL_END);
   tm.n_sel_all = (uint32_t)bt->l_all.size();
   tm.bits = bits ? 1u : 0u;
   tm.n_classes = bits ? (uint32_t)bt->crep.size() : 0u;
-  tm.n_slow = bt->h_stats[0];
+  tm.n_slow = bt->h_stats[KS_SLOW_TOTAL];
   tm.n_top = top ? (uint32_t)bt->n_all_dyn : 0u;
-  tm.n_top_fallback = top ? bt->h_stats[9] : 0u;
-  tm.top_kernel_ms = top ? ems(12, 13) : 0.f;
+  tm.n_top_fallback = top ? bt->h_stats[KS_TOP_FALLBACK] : 0u;
+  tm.top_kernel_ms = top ? ems(EV_TOP_BEGIN, EV_TOP_END) : 0.f;
   tm.n_cluster = (uint32_t)bt->l_cluster.size();
-  tm.n_cluster_order = spread_orders ? bt->h_stats[10] : 0u;
-  tm.cluster_kernel_ms = bt->l_cluster.empty() ? 0.f : ems(14, 15);
+  tm.n_cluster_order = spread_orders ? bt->h_stats[KS_CLUSTER_ORDER] : 0u;
+  tm.cluster_kernel_ms = bt->l_cluster.empty() ? 0.f : ems(EV_CLUSTER_BEGIN, EV_CLUSTER_END);
   tm.n_region = (uint32_t)bt->l_region.size();
-  tm.n_region_order = spread_orders ? bt->h_stats[11] : 0u;
-  tm.n_region_wide = bt->l_region_wide.empty() ? 0u : bt->h_stats[17];
+  tm.n_region_order = spread_orders ? bt->h_stats[KS_REGION_ORDER] : 0u;
+  tm.n_region_wide = bt->l_region_wide.empty() ? 0u : bt->h_stats[KS_REGION_WIDE_DONE];
 #if defined(KP_STAMPS) || defined(KP_SLOW_CHECK)
   {
     std::vector<unsigned long long> hv((size_t)kDbgSlots * kDbgSpread);
@@ -4521,8 +4533,10 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
             "kp slow: total %u overflow/dup %u scale-down %u wrap %u tie %u weight %u cluster %u "
             "(ties resolved block-parallel %u); class-order spread fallbacks: cluster %u region %u (stage A %u)"
             " check %u\n",
-            bt->h_stats[0], bt->h_stats[1], bt->h_stats[2], bt->h_stats[3], bt->h_stats[4], bt->h_stats[5],
-            bt->h_stats[6], bt->h_stats[7], bt->h_stats[12], bt->h_stats[13], bt->h_stats[14], bt->h_stats[15]);
+            bt->h_stats[KS_SLOW_TOTAL], bt->h_stats[SLOW_OVERFLOW_DUP], bt->h_stats[SLOW_SCALE_DOWN],
+            bt->h_stats[SLOW_WRAP], bt->h_stats[SLOW_TIE], bt->h_stats[SLOW_WEIGHT], bt->h_stats[SLOW_CLUSTER],
+            bt->h_stats[KS_TIE_BLOCK], bt->h_stats[KS_FB_CLUSTER], bt->h_stats[KS_FB_REGION],
+            bt->h_stats[KS_FB_REGION_A], bt->h_stats[KS_CHECK]);
   tm.pair_ms = ms_pair;
   tm.select_ms = ms_sel;
   tm.host_ms = th1 - th0;
@@ -4530,69 +4544,61 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   tm.total_ms = t1 - t0;
   e->times = tm;
   bt->sched_done = true;
+  auto common = [&](auto* r) {  // the fields the two result forms share
+    r->n_bindings = (uint64_t)B;
+    r->status = bt->h_status.data();
+    r->err_code = bt->h_err.data();
+    r->err_arg = bt->h_arg.data();
+    r->offsets = bt->h_offsets.data();
+    r->n_targets = tot_out;
+  };
   if (packed) {
-    pout->n_bindings = (uint64_t)B;
-    pout->status = bt->h_status.data();
-    pout->err_code = bt->h_err.data();
-    pout->err_arg = bt->h_arg.data();
-    pout->offsets = bt->h_offsets.data();
+    common(pout);
     pout->targets = bt->h_cidx;
-    pout->n_targets = tot_out;
     pout->wide_replicas = bt->h_crep;
     pout->n_wide = n_wide;
     pout->wide_offsets = bt->h_woff;
-    return KP_OK;
+  } else {
+    common(out);
+    out->cluster_idx = bt->h_cidx;
+    out->replicas = bt->h_crep;
   }
-  out->n_bindings = (uint64_t)B;
-  out->status = bt->h_status.data();
-  out->err_code = bt->h_err.data();
-  out->err_arg = bt->h_arg.data();
-  out->offsets = bt->h_offsets.data();
-  out->cluster_idx = bt->h_cidx;
-  out->replicas = bt->h_crep;
-  out->n_targets = tot_out;
   return KP_OK;
 }
-static int schedule_batch_impl(kp_engine* e, kp_batch* bt, kp_results* out) {
-  if (!out) return KP_EINVAL;
-  if (int rc = schedule_submit(e, bt)) return rc;
-  return schedule_finish(e, bt, out);
+
+// The wide and the packed entry points share one body per call. The one-shot call: exactly
+// one of out / pout is given, as for schedule_finish.
+static int schedule_both(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout) {
+  if (!out && !pout) return KP_EINVAL;
+  if (int rc = schedule_submit(e, bt, pout != nullptr)) return rc;
+  return schedule_finish(e, bt, out, pout);
 }
-int kp_schedule_batch(kp_engine* e, kp_batch* bt, kp_results* out) { return batch_fence(e, bt, schedule_batch_impl(e, bt, out)); }
-int kp_schedule_batch_submit(kp_engine* e, kp_batch* bt) {
+// The submit call; `who` names the entry point in the error texts.
+static int submit_call(kp_engine* e, kp_batch* bt, bool packed, const char* who) {
   if (e && e->prof) {
-    e->err = "kp_schedule_batch_submit: per-kernel profiling covers kp_schedule_batch only";
+    e->err = std::string(who) + ": per-kernel profiling covers kp_schedule_batch only";
     return KP_EINVAL;
   }
-  if (bt && bt->pend.live) {
-    e->err = "kp_schedule_batch_submit: the batch's previous call is not collected";
+  if (!e || !bt) return KP_EINVAL;
+  if (bt->pend.live) {
+    e->err = std::string(who) + ": the batch's previous call is not collected";
     return KP_ESTATE;
   }
-  return batch_fence(e, bt, schedule_submit(e, bt));
+  return batch_fence(e, bt, schedule_submit(e, bt, packed));
+}
+int kp_schedule_batch(kp_engine* e, kp_batch* bt, kp_results* out) { return batch_fence(e, bt, schedule_both(e, bt, out, nullptr)); }
+int kp_schedule_batch_submit(kp_engine* e, kp_batch* bt) {
+  return submit_call(e, bt, false, "kp_schedule_batch_submit");
 }
 int kp_schedule_batch_collect(kp_engine* e, kp_batch* bt, kp_results* out) {
-  return batch_fence(e, bt, schedule_finish(e, bt, out));
+  return batch_fence(e, bt, schedule_finish(e, bt, out, nullptr));
 }
-
 // The packed result form (kp_results_packed): the same calls with packed = true.
-static int schedule_batch_packed_impl(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
-  if (!out) return KP_EINVAL;
-  if (int rc = schedule_submit(e, bt, true)) return rc;
-  return schedule_finish(e, bt, nullptr, out);
-}
 int kp_schedule_batch_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
-  return batch_fence(e, bt, schedule_batch_packed_impl(e, bt, out));
+  return batch_fence(e, bt, schedule_both(e, bt, nullptr, out));
 }
 int kp_schedule_batch_submit_packed(kp_engine* e, kp_batch* bt) {
-  if (e && e->prof) {
-    e->err = "kp_schedule_batch_submit_packed: per-kernel profiling covers kp_schedule_batch only";
-    return KP_EINVAL;
-  }
-  if (e && bt && bt->pend.live) {
-    e->err = "kp_schedule_batch_submit_packed: the batch's previous call is not collected";
-    return KP_ESTATE;
-  }
-  return batch_fence(e, bt, schedule_submit(e, bt, true));
+  return submit_call(e, bt, true, "kp_schedule_batch_submit_packed");
 }
 int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
   return batch_fence(e, bt, schedule_finish(e, bt, nullptr, out));
@@ -5205,30 +5211,22 @@ struct DevNodes {
       reqs.insert(reqs.end(), c.reqs.begin(), c.reqs.end());
       vals.insert(vals.end(), c.vals.begin(), c.vals.end());
     }
-    ar.add(&d_flags, std::max<size_t>(1, h.flags.size()));
-    ar.add(&d_name, std::max<size_t>(1, h.name.size()));
-    ar.add(&d_loff, h.lbl_off.size());
-    ar.add(&d_lbl, std::max<size_t>(1, h.lbl.size()));
-    ar.add(&d_lint, std::max<size_t>(1, h.lbl_int.size()));
-    ar.add(&d_lok, std::max<size_t>(1, h.lbl_int_ok.size()));
-    ar.add(&d_toff, h.tnt_off.size());
-    ar.add(&d_tnt, std::max<size_t>(1, h.tnt.size()));
-    ar.add(&d_sel, std::max<size_t>(1, sel.size()));
-    ar.add(&d_tols, std::max<size_t>(1, tols.size()));
-    ar.add(&d_toffs, std::max<size_t>(1, toffs.size()));
-    ar.add(&d_reqs, std::max<size_t>(1, reqs.size()));
-    ar.add(&d_vals, std::max<size_t>(1, vals.size()));
+    ar.add(&d_flags, h.flags.data(), h.flags.size(), 1);
+    ar.add(&d_name, h.name.data(), h.name.size(), 1);
+    ar.add(&d_loff, h.lbl_off.data(), h.lbl_off.size());
+    ar.add(&d_lbl, h.lbl.data(), h.lbl.size(), 1);
+    ar.add(&d_lint, h.lbl_int.data(), h.lbl_int.size(), 1);
+    ar.add(&d_lok, h.lbl_int_ok.data(), h.lbl_int_ok.size(), 1);
+    ar.add(&d_toff, h.tnt_off.data(), h.tnt_off.size());
+    ar.add(&d_tnt, h.tnt.data(), h.tnt.size(), 1);
+    ar.add(&d_sel, sel.data(), sel.size(), 1);
+    ar.add(&d_tols, tols.data(), tols.size(), 1);
+    ar.add(&d_toffs, toffs.data(), toffs.size(), 1);
+    ar.add(&d_reqs, reqs.data(), reqs.size(), 1);
+    ar.add(&d_vals, vals.data(), vals.size(), 1);
   }
-  int upload(dev::stream_t st, const HostNodes& h, const std::vector<HostClaim>& cl, uint64_t n) {
-    auto up = [&](void* dd, const void* hp, size_t bytes) { return bytes ? dev::h2d(dd, hp, bytes, st) : 0; };
-    if (up(d_flags, h.flags.data(), 4 * h.flags.size()) || up(d_name, h.name.data(), 4 * h.name.size()) ||
-        up(d_loff, h.lbl_off.data(), 4 * h.lbl_off.size()) || up(d_lbl, h.lbl.data(), 8 * h.lbl.size()) ||
-        up(d_lint, h.lbl_int.data(), 8 * h.lbl_int.size()) || up(d_lok, h.lbl_int_ok.data(), h.lbl_int_ok.size()) ||
-        up(d_toff, h.tnt_off.data(), 4 * h.tnt_off.size()) || up(d_tnt, h.tnt.data(), 4 * h.tnt.size()) ||
-        up(d_sel, sel.data(), 8 * sel.size()) || up(d_tols, tols.data(), sizeof(Tol) * tols.size()) ||
-        up(d_toffs, toffs.data(), 4 * toffs.size()) || up(d_reqs, reqs.data(), sizeof(NodeReq) * reqs.size()) ||
-        up(d_vals, vals.data(), 4 * vals.size()))
-      return -1;
+  // (after the arena's alloc()) the node view and each claim's program over the sub-buffers
+  void views(const std::vector<HostClaim>& cl, uint64_t n) {
     v = NodeView{n, d_flags, d_name, d_loff, d_lbl, d_lint, d_lok, d_toff, d_tnt};
     for (size_t k = 0; k < cl.size(); k++) {
       ClaimProg p{};
@@ -5244,7 +5242,6 @@ struct DevNodes {
       p.vals = d_vals + o_val[k];
       progs.push_back(p);
     }
-    return 0;
   }
 };
 void split128(k8s::i128 v, int64_t* hi, uint64_t* lo) {
@@ -5311,17 +5308,14 @@ int kp_model_grades(kp_engine* e, const kp_resource_model* models, uint32_t n_mo
   int64_t *d_mh, *d_vh;
   uint64_t *d_ml, *d_vl;
   unsigned long long* d_cnt;
-  a.add(&d_mh, mh.size());
-  a.add(&d_ml, ml.size());
-  a.add(&d_vh, std::max<size_t>(1, vh.size()));
-  a.add(&d_vl, std::max<size_t>(1, vl.size()));
+  a.add(&d_mh, mh.data(), mh.size());
+  a.add(&d_ml, ml.data(), ml.size());
+  a.add(&d_vh, vh.data(), vh.size(), 1);
+  a.add(&d_vl, vl.data(), vl.size(), 1);
   a.add(&d_cnt, K);
   HIPCHK(a.alloc());
   dev::stream_t st = e->stream;
-  HIPCHK(dev::h2d(d_mh, mh.data(), 8 * mh.size(), st));
-  HIPCHK(dev::h2d(d_ml, ml.data(), 8 * ml.size(), st));
-  HIPCHK(dev::h2d(d_vh, vh.data(), 8 * vh.size(), st));
-  HIPCHK(dev::h2d(d_vl, vl.data(), 8 * vl.size(), st));
+  HIPCHK(a.upload(st));
   HIPCHK(dev::fill(d_cnt, 0, 8 * (size_t)K, st));
   GradesArgs A{K, NR, d_mh, d_ml, d_vh, d_vl, n, d_cnt};
   HIPCHK(dev::grades(st, A));
@@ -5465,24 +5459,24 @@ static int node_job_run(kp_engine* e, NodeJob& J, const kp_node_claim* est_claim
   int32_t* d_out;
   ar.add(&d_progs, std::max<size_t>(1, NP));
   ar.add(&d_args, 1);
-  ar.add(&d_avail, std::max<size_t>(1, J.avail.size()));
-  ar.add(&d_present, std::max<size_t>(1, J.present.size()));
+  ar.add(&d_avail, J.avail.data(), J.avail.size(), 1);
+  ar.add(&d_present, J.present.data(), J.present.size(), 1);
   ar.add(&d_match, std::max<size_t>(1, (size_t)KS * J.A.n));
   ar.add(&d_out, 1);
   ar.add(&d_ovf, 1);
   ar.add(&d_sum, 1);
   HIPCHK(ar.alloc());
   dev::stream_t st = e->stream;
-  HIPCHK(dn.upload(st, J.hn, J.cl, J.A.n));
+  HIPCHK(ar.upload(st));
+  dn.views(J.cl, J.A.n);
   J.A.avail = d_avail;
   J.A.present = d_present;
   J.A.match = d_match;
   J.A.out = d_out;
   J.A.ovf = d_ovf;
+  // (the claim programs and the arguments hold device pointers, known after alloc(): direct copies)
   if (NP) HIPCHK(dev::h2d(d_progs, dn.progs.data(), sizeof(ClaimProg) * NP, st));
   HIPCHK(dev::h2d(d_args, &J.A, sizeof(J.A), st));
-  if (!J.avail.empty()) HIPCHK(dev::h2d(d_avail, J.avail.data(), 8 * J.avail.size(), st));
-  if (!J.present.empty()) HIPCHK(dev::h2d(d_present, J.present.data(), 4 * J.present.size(), st));
   HIPCHK(dev::fill(d_out, 0, 4, st));
   HIPCHK(dev::fill(d_ovf, 0, 4, st));
   if (KS > 0 && J.A.n > 0) {

@@ -407,7 +407,7 @@ KP_FI void body_pair(const BLK& B, int blk, unsigned char* smem, const SnapView&
 KP_HD inline void flag_slow(const KArgs& a, int b, int why) {
   a.slow[b] = why;
   a.sink.count[b] = 0;
-  const uint32_t i = kp_atomic_add(&a.stats[0], 1u);
+  const uint32_t i = kp_atomic_add(&a.stats[KS_SLOW_TOTAL], 1u);
   a.slow_ids[i] = b;
   kp_atomic_add(&a.stats[why], 1u);
 }
@@ -1677,7 +1677,7 @@ KP_HD void body_slow(const BLK& B, int blk, int grid, unsigned char* smem, const
   int32_t* pos = (int32_t*)(items + a.s.Cp);
   unsigned char* ser = (unsigned char*)(pos + a.s.Cp);
   // the select kernels appended the flagged bindings to slow_ids (same stream: complete)
-  const int nslow = (int)*(volatile uint32_t*)&a.stats[0];
+  const int nslow = (int)*(volatile uint32_t*)&a.stats[KS_SLOW_TOTAL];
   if (blk >= nslow || blk >= a.n) return;  // (block-uniform) a slot without a binding is never touched
   for (int i = B.tid(); i < a.s.Cp; i += B.nth()) pos[i] = -1;
   B.sync();
@@ -1783,7 +1783,7 @@ KP_HD void body_slow(const BLK& B, int blk, int grid, unsigned char* smem, const
       if (w2 == SLOW_NONE) {
         if (B.tid() == 0) {
           a.slow[b] = 0;
-          kp_atomic_add(&a.stats[7], 1u);  // resolved block-parallel
+          kp_atomic_add(&a.stats[KS_TIE_BLOCK], 1u);  // resolved block-parallel
         }
         KP_STAMP(x, 7);
         continue;

@@ -21,8 +21,8 @@ struct KArgs {
   const int32_t* bcls;
   Sink sink;
   int32_t* slow;          // [B] SLOW_* reason the binding needs k_slow for (0: none)
-  int32_t* slow_ids;      // bindings flagged for k_slow, [0, stats[0]) (append order)
-  uint32_t* stats;        // [0]: bindings flagged for the serial path, [SLOW_*]: by reason
+  int32_t* slow_ids;      // bindings flagged for k_slow, [0, stats[KS_SLOW_TOTAL]) (append order)
+  uint32_t* stats;        // the batch's counters, [kStatSlots] (KS_* below)
   unsigned long long* dbg;  // diagnostic build only: phase cycle sums (nullptr otherwise)
   // set: the launch covers list[0, *n_dev) with a grid-stride loop (a list another
   // kernel appended to, e.g. k_select_top's fallback list); n is its capacity
@@ -39,6 +39,26 @@ struct KArgs {
   // class order and class flags load one dependent global load earlier)
   const int32_t* lcls = nullptr;
 };
+
+// The batch's device counters (KArgs::stats; kp_batch::h_stats is their host copy after a
+// schedule call). The kernels index [KS_SLOW_TOTAL], [SLOW_* reason] and [KS_TIE_BLOCK]
+// themselves; the host hands the others out as pointers (TopArgs, OrderArgs, n_dev, n_order).
+enum : int {
+  KS_SLOW_TOTAL = 0,  // bindings flagged for the serial path; [1..6]: by SLOW_* reason (kp_paths.h)
+  KS_TIE_BLOCK = 7,         // of the SLOW_TIE ones, resolved block-parallel
+  // (slot 8 is unused: the component-set overflow is reported per class, kp_batch::d_sets_ovf)
+  KS_TOP_FALLBACK = 9,      // k_select_top's fallback list length
+  KS_CLUSTER_ORDER = 10,    // cluster-spread bindings selected over the class order
+  KS_REGION_ORDER = 11,     // region-spread bindings selected over the class order
+  KS_FB_CLUSTER = 12,       // k_spread_order's fallback list length, cluster positions
+  KS_FB_REGION = 13,        // ... region positions
+  KS_FB_REGION_A = 14,      // k_region_a_order's fallback list length
+  KS_CHECK = 15,            // diagnostic builds' check counter
+  KS_TOP_OVERFLOW = 16,     // k_select_top's capacity overflows (the top_cap_mid launch)
+  KS_REGION_WIDE_DONE = 17  // bindings k_region_wide scheduled or errored
+};
+constexpr int kStatSlots = 20;
+static_assert((int)SLOW_CLUSTER < (int)KS_TIE_BLOCK, "the SLOW_* reasons index the counters below KS_TIE_BLOCK");
 
 enum : int {
   SEL_LAUNCH_ALL = 0,

@@ -21,7 +21,7 @@ namespace kp {
 
 constexpr int kRegionMax = 256;
 
-// Reasons a binding leaves the fast paths for the exact serial path (stats[reason]).
+// Reasons a binding leaves the fast paths for the exact serial path (KArgs::stats[reason], kp_launch.h).
 enum : int { SLOW_NONE = 0, SLOW_OVERFLOW_DUP = 1, SLOW_SCALE_DOWN = 2, SLOW_WRAP = 3, SLOW_TIE = 4, SLOW_WEIGHT = 5,
              SLOW_CLUSTER = 6,
              // a.slow[b] of a region-spread binding whose selection outgrew stage B's LDS lists:

@@ -433,6 +433,24 @@ def test_submit_collect_host_build(cpusim_engine):
     check_submit_collect(cpusim_engine, 300, 300)
 
 
+def test_submit_refused_while_pending_host_build(cpusim_engine):
+    """Both submit calls refuse a batch whose previous call is not collected with KP_ESTATE
+    (-5), each under its own name (one body in engine.cpp serves the two)."""
+    u = synth.Universe(8, 5, 64, 0, 8)
+    snap = Snapshot.from_structs(cpusim_engine, u.clusters, u.n_clusters, u.names, api.options())
+    b = Batch(snap, structs=u.binding_slice(0, 8))
+    for first, collect in ((b.submit, b.collect), (b.submit_packed, b.collect_packed)):
+        first()
+        with pytest.raises(EngineError, match=r"rc=-5: kp_schedule_batch_submit: the batch's previous call is not collected"):
+            b.submit()
+        with pytest.raises(EngineError,
+                           match=r"rc=-5: kp_schedule_batch_submit_packed: the batch's previous call is not collected"):
+            b.submit_packed()
+        collect()  # the pending call is untouched by the refusals
+    b.close()
+    snap.close()
+
+
 @pytest.mark.gpu
 def test_submit_collect_gpu(gpu_engine):
     check_submit_collect(gpu_engine, 5000, 2000)
