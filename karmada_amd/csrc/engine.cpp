@@ -1,193 +1,13 @@
-// engine.cpp — host side of the kp placement engine: the C-ABI of
-// include/kp/kp_api.h, the snapshot/binding packer, kernel orchestration on one
-// HIP stream, and the host-kept selectGroups step of region spreading.
-#include "kp_dev.h"
-
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <deque>
-#include <condition_variable>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <new>
-#include <tuple>
-#include <type_traits>
-#include <string>
-#include <string_view>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/kp/kp_api.h"
-#include "k8s.h"
-#include "kp_env.h"
-#include "kp_layout.h"
-#include "kp_launch.h"
+// engine.cpp — host side of the kp placement engine: the C-ABI of include/kp/kp_api.h except
+// the node estimator (nodes.cpp). The snapshot/binding packer, kernel orchestration on one HIP
+// stream, the host-kept selectGroups step, and the one definition of kp_host.h's shared state.
+#include "kp_host.h"
 #include "kp_paths.h"
 #include "kp_pdq.h"
-#include "kp_sets.h"
-#include "kp_nodes.h"
 #include "kp_top.h"
 
-using namespace kp;
+namespace kp::host {
 
-namespace {
-
-std::string S(const kp_str& s) { return (s.ptr && s.len) ? std::string(s.ptr, s.len) : std::string(); }
-std::string_view SV(const kp_str& s) { return (s.ptr && s.len) ? std::string_view(s.ptr, s.len) : std::string_view(); }
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// String-keyed hash table with string_view lookups for the packing hot path (names,
-// dictionary strings, memo keys): open addressing with linear probing over a
-// power-of-two slot array kept at most half full, one multiply-xorshift hash over
-// 8-byte words per lookup, entries in a deque (stable addresses). find() returns the
-// entry or nullptr (== end()); it->first / it->second as with std::unordered_map.
-inline uint64_t sv_hash(std::string_view v) {
-  const unsigned char* p = (const unsigned char*)v.data();
-  size_t n = v.size();
-  uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)n;
-  for (; n >= 8; n -= 8, p += 8) {
-    uint64_t w;
-    memcpy(&w, p, 8);
-    h = (h ^ w) * 0xff51afd7ed558ccdull;
-    h ^= h >> 32;
-  }
-  uint64_t w = 0;
-  memcpy(&w, p, n);
-  h = (h ^ w) * 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 29;
-  return h | 1;  // 0 marks an empty slot
-}
-template <class V>
-class SvMap {
- public:
-  struct Entry {
-    std::string first;
-    V second;
-  };
-  Entry* find(std::string_view k) {
-    if (slots_.empty()) return nullptr;
-    const uint64_t h = sv_hash(k);
-    for (size_t i = h & mask_;; i = (i + 1) & mask_) {
-      const Slot& sl = slots_[i];
-      if (sl.h == 0) return nullptr;
-      if (sl.h == h && ent_[sl.i].first == k) return &ent_[sl.i];
-    }
-  }
-  const Entry* find(std::string_view k) const { return const_cast<SvMap*>(this)->find(k); }
-  Entry* end() const { return nullptr; }
-  template <class K, class W>
-  std::pair<Entry*, bool> emplace(K&& k, W&& v) {
-    if (Entry* e = find(std::string_view(k))) return {e, false};
-    if (2 * (ent_.size() + 1) > slots_.size()) grow();
-    ent_.push_back(Entry{std::string(std::forward<K>(k)), V(std::forward<W>(v))});
-    put(sv_hash(ent_.back().first), (uint32_t)(ent_.size() - 1));
-    return {&ent_.back(), true};
-  }
-  V& operator[](std::string_view k) { return emplace(std::string(k), V()).first->second; }
-  size_t size() const { return ent_.size(); }
-
- private:
-  struct Slot {
-    uint64_t h = 0;
-    uint32_t i = 0;
-  };
-  std::vector<Slot> slots_;
-  std::deque<Entry> ent_;
-  size_t mask_ = 0;
-  void put(uint64_t h, uint32_t i) {
-    size_t j = h & mask_;
-    while (slots_[j].h != 0) j = (j + 1) & mask_;
-    slots_[j] = Slot{h, i};
-  }
-  void grow() {
-    const size_t cap = std::max<size_t>(16, 2 * slots_.size());
-    slots_.assign(cap, Slot{});
-    mask_ = cap - 1;
-    for (uint32_t i = 0; i < (uint32_t)ent_.size(); i++) put(sv_hash(ent_[i].first), i);
-  }
-};
-
-struct Dict {
-  SvMap<int32_t> m;
-  std::vector<std::string> names;
-  int32_t add(const std::string& s) {
-    auto it = m.find(s);
-    if (it != m.end()) return it->second;
-    int32_t id = (int32_t)names.size();
-    m.emplace(s, id);
-    names.push_back(s);
-    return id;
-  }
-  int32_t get(std::string_view s) const {
-    auto it = m.find(s);
-    return it == m.end() ? -1 : it->second;
-  }
-};
-
-// Process-wide pools of freed batch buffers: a batch's device arena (per device)
-// and its page-locked result buffers go back here on kp_batch_destroy and the next
-// batch of a fitting size takes them, so a stream of batches pays hipMalloc /
-// hipHostMalloc (and the frees) once. A block is reused for requests of at least
-// half its size. Each pool (one per device, one for page-locked host memory) keeps
-// at most kPoolKeep blocks and kPoolBytes (device) / kPoolHostBytes (host) bytes,
-// oldest evicted first: several engines' batches in flight (bench lanes, kp_multi)
-// each hold an arena and two host buffers.
-struct BufPool {
-  static constexpr size_t kPoolKeep = 32;
-  static constexpr size_t kPoolBytes = (size_t)16 << 30;     // per device (288 GB of HBM)
-  static constexpr size_t kPoolHostBytes = (size_t)4 << 30;  // page-locked host memory
-  std::mutex mu;
-  std::vector<std::tuple<int, void*, size_t>> free;  // (device or -1 for host, pointer, bytes), oldest first
-  void* get(int dev_id, size_t bytes, size_t* got) {
-    std::lock_guard<std::mutex> g(mu);
-    size_t best = (size_t)-1;
-    for (size_t i = 0; i < free.size(); i++) {
-      auto& [d, p, n] = free[i];
-      if (d == dev_id && n >= bytes && n <= 2 * bytes + (1u << 20) && (best == (size_t)-1 || n < std::get<2>(free[best])))
-        best = i;
-    }
-    if (best == (size_t)-1) return nullptr;
-    void* p = std::get<1>(free[best]);
-    *got = std::get<2>(free[best]);
-    free.erase(free.begin() + (long)best);
-    return p;
-  }
-  void put(int dev_id, void* p, size_t bytes) {
-    if (!p) return;
-    std::vector<std::tuple<int, void*, size_t>> drop;
-    {
-      std::lock_guard<std::mutex> g(mu);
-      free.emplace_back(dev_id, p, bytes);
-      size_t cnt = 0, tot = 0;
-      for (auto& f : free)
-        if (std::get<0>(f) == dev_id) cnt++, tot += std::get<2>(f);
-      const size_t cap = dev_id < 0 ? kPoolHostBytes : kPoolBytes;
-      for (size_t i = 0; i < free.size() && (cnt > kPoolKeep || tot > cap);) {  // the oldest of this pool go
-        if (std::get<0>(free[i]) != dev_id) {
-          i++;
-          continue;
-        }
-        cnt--, tot -= std::get<2>(free[i]);
-        drop.push_back(free[i]);
-        free.erase(free.begin() + (long)i);
-      }
-    }
-    for (auto& d : drop) {
-      if (std::get<0>(d) < 0) dev::host_release(std::get<1>(d));
-      else dev::release(std::get<1>(d));
-    }
-  }
-};
 BufPool& buf_pool() {
   static BufPool* p = new BufPool();  // never destroyed: buffers may return during exit
   return *p;
@@ -200,391 +20,22 @@ void* pinned_get(size_t bytes, size_t* got) {
   return p;
 }
 
-// One device allocation carved into aligned sub-buffers. pool_dev >= 0: the
-// allocation comes from (and returns to) the batch-buffer pool of that device.
-// A sub-buffer filled from host data is registered with its source (the second add):
-// upload() then copies what was registered, so the bytes reserved and the bytes copied
-// come from one count and the destination's element type.
-struct Arena {
-  struct Req {
-    void** p;
-    size_t bytes;     // reserved
-    const void* src;  // host source, or null for a work buffer
-    size_t src_bytes;
-  };
-  std::vector<Req> req;
-  void* base = nullptr;
-  size_t total = 0;
-  int pool_dev = -1;
-  size_t got = 0;
-  template <class T>
-  void add(T** p, size_t count) {
-    req.push_back({(void**)p, count * sizeof(T), nullptr, 0});
-  }
-  // *p[0, count) = src[0, count) at upload(); max(count, min_count) elements are reserved
-  // (a list that may be empty keeps a valid pointer). src must stay alive until the
-  // stream upload() ran on is synchronised.
-  template <class T>
-  void add(T** p, const std::type_identity_t<T>* src, size_t count, size_t min_count = 0) {
-    req.push_back({(void**)p, std::max(count, min_count) * sizeof(T), src, count * sizeof(T)});
-  }
-  static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-  int alloc() {
-    total = 0;
-    for (auto& r : req) total += pad(r.bytes);
-    if (total == 0) total = 256;
-    if (pool_dev >= 0) base = buf_pool().get(pool_dev, total, &got);
-    if (!base) {
-      if (dev::alloc(&base, total)) return -1;
-      got = total;
-    }
-    char* p = (char*)base;
-    for (auto& r : req) {
-      *r.p = p;
-      p += pad(r.bytes);
-    }
-    return 0;
-  }
-  // The registered host sources copied to their sub-buffers on `st` (after alloc()).
-  int upload(dev::stream_t st) {
-    for (auto& r : req) {
-      if (r.src && dev::h2d(*r.p, r.src, r.src_bytes, st)) return -1;
-      r.src = nullptr;  // (copied once: the source need not outlive the caller's sync)
-    }
-    return 0;
-  }
-  // One block of `bytes` with no sub-buffers (a replica's copy of another arena).
-  int alloc_raw(size_t bytes) {
-    req.clear();
-    total = bytes ? bytes : 256;
-    got = total;
-    return dev::alloc(&base, total);
-  }
-  void drop() {
-    if (!base) return;
-    if (pool_dev >= 0) buf_pool().put(pool_dev, base, got);
-    else dev::release(base);
-    base = nullptr;
-  }
-  void reset() {
-    drop();
-    req.clear();
-    total = 0;
-  }
-  ~Arena() { drop(); }
-};
-
-#define HIPCHK(x)                                                            \
-  do {                                                                       \
-    if ((x) != 0) {                                                          \
-      e->err = std::string(#x) + ": " + dev::last_error();                   \
-      return KP_EDEVICE;                                                     \
-    }                                                                        \
-  } while (0)
-
-}  // namespace
-
-// std::allocator that leaves trivial elements uninitialized on resize: the packer
-// writes every BindHdr itself (in parallel, so the pages are first touched there),
-// and a value-initializing resize would zero 160 B per binding on one thread.
-template <class T>
-struct NoInitAlloc : std::allocator<T> {
-  template <class U>
-  struct rebind {
-    using other = NoInitAlloc<U>;
-  };
-  NoInitAlloc() = default;
-  template <class U>
-  NoInitAlloc(const NoInitAlloc<U>&) {}
-  template <class U>
-  void construct(U* p) noexcept {
-    ::new ((void*)p) U;
-  }
-  template <class U, class... A>
-  void construct(U* p, A&&... a) {
-    ::new ((void*)p) U(std::forward<A>(a)...);
-  }
-};
-
-// ============================================================================
-// Engine / snapshot / batch objects
-// ============================================================================
-// The engine's events (kp_engine::ev), one per event a schedule call records; BEGIN / END
-// pairs time a stage for kp_last_stage_times, the others order the three streams.
-enum : int {
-  EV_FILLS = 0,       // stream: the counters are cleared (every kernel waits for it)
-  EV_SELECT_BEGIN,    // stream: the rows are complete ...
-  EV_SELECT_END,      // ... to the end of the last select kernel and k_slow
-  EV_ROWS_BEGIN,      // stream2: the estimator rows and the filter ...
-  EV_ROWS_END,        // ... complete (stream and stream3 wait for it)
-  EV_CLASS_ROWS,      // stream2: every class row is written (k_class_order's input)
-  EV_CLASS_ORDER,     // stream3: k_class_order done (stream2 waits for it)
-  EV_SEL_ALL_BEGIN,   // stream2: the SEL_ALL kernels ...
-  EV_SEL_ALL_END,     // ... (k_slow and the results wait for it)
-  EV_SLOW_END,        // stream3: k_slow done (the results wait for it)
-  EV_TOP_LARGE,       // stream3: k_select_top's large slice done (its fallbacks follow on stream2)
-  EV_TOP_BEGIN,       // stream2: k_select_top's launches ...
-  EV_TOP_END,
-  EV_CLUSTER_BEGIN,   // stream3: the cluster-spread kernels ...
-  EV_CLUSTER_END,
-  kEngineEvents
-};
-
-struct kp_engine {
-  int device = 0;
-  dev::stream_t stream = nullptr;   // select kernels, copies (the batch's result order)
-  dev::stream_t stream2 = nullptr;  // pair kernel, then the SEL_ALL select kernel
-  dev::stream_t stream3 = nullptr;  // the cluster-spread select kernel, beside the other selects
-  dev::event_t ev[kEngineEvents] = {};
-  std::string err;
-  kp_stage_times times{};
-  struct {  // kp_schedule_affinities results
-    std::vector<int32_t> status, err, idx, attempts;
-    std::vector<int64_t> arg;
-    std::vector<uint64_t> offsets;
-    std::vector<uint32_t> cidx;
-    std::vector<int32_t> rep;
-  } aff;
-  struct {  // kp_fit_diagnosis_batch results
-    std::vector<uint64_t> binding, offsets;
-    std::vector<uint32_t> reason, taint_ref, count, n_fit, n_del;
-  } diag;
-  int n_threads = 8;
-  size_t max_lds = 65536;
-  // k_select_top (kp_top.h): on, and its subset capacity per binding (LDS entries);
-  // KP_TOP=0 / KP_TOP_CAP=<n> at engine creation (tests, tuning)
-  bool top_on = true;
-  int top_cap = 832;       // subset capacity of the large slice (LDS: 8 workgroups of two waves per CU)
-  int top_cap_small = 256;  // ... and of the small one (bindings needing <= kTopSmallNeed)
-  // the large-slice bindings run at this capacity first (more waves per CU); those whose
-  // subset outgrows it run again at top_cap (0 / >= top_cap: one launch at top_cap)
-  int top_cap_mid = 0;
-  bool top_split = true;    // the two slices' launches on two streams (KP_TOP_SPLIT=0: one)
-  bool slow_order = true;   // k_slow orders candidates from the class orders (KP_SLOW_ORDER=0: sorts)
-  // per-kernel timing of kp_schedule_batch (kp_engine_set_profile): an event pair
-  // around every launch on its own stream, folded by kernel name after the batch
-  struct KProf {
-    const char* name;
-    uint64_t units;  // bindings (or rows) the launch covered
-    int units_stat;  // >= 0: the count is device-side, h_stats[units_stat] (KS_*)
-  };
-  bool prof = false;
-  uint64_t submit_seq = 0;  // schedule calls submitted on this engine (stage timing validity)
-  std::vector<dev::event_t> pev;
-  std::vector<KProf> pk;
-  std::vector<kp_kernel_time> ktimes;
-};
-
 // Snapshot epochs: unique per snapshot object and renewed when kp_snapshot_update grows
 // its dictionaries, so packed records (kp_pack_cache) know which ids they resolved against.
-static uint64_t next_snap_epoch() {
+uint64_t next_snap_epoch() {
   static std::atomic<uint64_t> n{0};
   return ++n;
 }
-struct kp_snapshot {
-  kp_engine* e = nullptr;
-  uint64_t epoch = next_snap_epoch();
-  kp_options opts{};
-  int C = 0, Cp = 0, W = 0;
-  Dict str, keys, gvk, res, regions;
-  SvMap<int32_t> rank_of;  // cluster name -> rank
-  std::vector<uint32_t> perm;                        // rank -> caller index
-  std::vector<int32_t> inv;                          // caller index -> rank
-  int32_t rid_cpu = -1, rid_mem = -1, rid_eph = -1;
-  int n_tmpl = 0, kmax = 0;
-  int est_kind = 0;  // EST_* pair-kernel instance the clusters allow (snapshot_est_kind)
-  std::vector<std::string> names;  // cluster names in rank order
-  std::vector<unsigned char> blob;  // kp_snapshot_export buffer
-  // host copies
-  std::vector<uint32_t> flags;
-  std::vector<int32_t> provider, region, region_idx, zone_off, zone_ids, label_val, taint_off, taint_key, taint_val,
-      taint_eff, mgrp_off, mgrp_tid, mg_tid, mg_cnt;
-  std::vector<int64_t> provider_int, region_int, allowed, avail, mgrp_cnt, tmpl;
-  std::vector<int64_t> qa;  // [R][Cp] quantityAsInt64 availability, kQaAbsent where not allocatable
-  std::vector<uint64_t> api_bits;
-  Arena dev;
-  SnapView view{};
-};
 
-// diagnostic builds: phase stamps and counters, kDbgSlots x kDbgSpread (kp_select.h)
-// The state schedule_submit leaves for schedule_finish (one submitted call per batch).
-struct SchedPend {
-  bool live = false, empty = false, bits = false, top = false, spread_orders = false;
-  bool packed = false;  // the call returns kp_results_packed (kp_schedule_batch_submit_packed)
-  int fast = 0;
-  double t0 = 0, th0 = 0, th1 = 0;
-  uint64_t seq = 0;
-  dev::event_t ev = nullptr;  // recorded after the call's last read-back (kept across calls)
-};
-
-struct kp_batch {
-  kp_snapshot* snap = nullptr;
-  int B = 0;
-  std::vector<BindHdr, NoInitAlloc<BindHdr>> hdr;
-  std::vector<int32_t> ipool;
-  std::vector<int64_t> lpool;
-  std::vector<Tol> tols;
-  std::vector<Prog> progs;
-  std::vector<Instr> instrs;
-  std::vector<int32_t> l_all, l_cluster, l_region, l_slow, l_cs;  // l_cs: cluster + region bindings
-  int n_all_dyn = 0;  // l_all = [other strategies | StaticWeight]: the first n_all_dyn are not StaticWeight
-  int n_top_small = 0;  // of those, the first n_top_small take k_select_top's small slice
-  int n_static = 0;   // of the StaticWeight ones, the first n_static take k_select_static (static_ok)
-  uint64_t out_cap = 0;
-  std::vector<uint8_t> route;     // RT_* per binding (pack_parallel)
-  int max_tgt = 0, max_tiers = 1;  // over the batch's headers (pack_parallel)
-  Arena dev;
-  BatchView view{};
-  // device work buffers
-  uint64_t* fmask = nullptr;
-  int32_t* est = nullptr;  // [B][Cp] per-binding rows (allocated on first use: rows mode, diagnosis entries)
-  // estimator classes (kp_filter.h): class of each binding (0 = non-workload) and
-  // a representative binding per class; their raw GeneralEstimator rows [n][Cp]
-  std::vector<int32_t> bcls, crep;
-  int32_t *d_bcls = nullptr, *d_crep = nullptr, *cls_rows = nullptr;
-  int32_t* d_all_cls = nullptr;  // the estimator class of each l_all entry (KArgs::lcls)
-  std::vector<int32_t> l_all_cls;
-  // Estimator classes serving one binding, in a batch without class orders (est_single):
-  // their rows hold only that binding's feasible clusters, written after k_filter
-  // (k_est_class over l_cls_single with the feasibility rows); l_cls_full: the others.
-  bool est_single = false;
-  std::vector<int32_t> l_cls_full, l_cls_single;
-  int32_t *d_cls_full = nullptr, *d_cls_single = nullptr;
-  // The other estimators' answers (kp_batch_create_estimates; all empty / null for a batch
-  // without them, which allocates, uploads and launches nothing for it): cls_est[class] =
-  // the class's row of d_est_rows ([n_rows][Cp], by cluster rank, -1 in the padding), -1
-  // for none; l_est_cls: the classes that have one (k_est_extra's list in bits mode).
-  std::vector<int32_t> cls_est, l_est_cls;
-  int32_t *d_cls_est = nullptr, *d_est_cls = nullptr, *d_est_rows = nullptr;
-  // The out-of-tree filter plugins' verdicts (kp_batch_create_filters; empty / null for a
-  // batch without rows, which allocates, uploads and launches nothing for them): l_flt =
-  // the bindings that have a row, (binding, row id) in binding order (k_filter_extra's
-  // list); d_flt_rows[n_rows][W] words by cluster rank, zero bits in the padding, fixed
-  // for the batch's lifetime. flt_plugins: how many registered plugins the answers fold
-  // in (the schedule calls' gate against kp_options.n_out_of_tree_plugins).
-  std::vector<FltPair> l_flt;
-  FltPair* d_flt_list = nullptr;
-  uint64_t* d_flt_rows = nullptr;
-  uint32_t flt_plugins = 0;
-  // component-set classes (BF_SETS): class id and resolved component list of each;
-  // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
-  // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)
-  // k_select_top: per-class candidate orders, row sums and walkability; its fallback list
-  uint64_t* d_ord = nullptr;
-  int64_t* d_ctot = nullptr;
-  int32_t *d_cok = nullptr, *d_fb = nullptr, *d_ofb = nullptr;
-  int32_t *d_fbc = nullptr, *d_fbr = nullptr;  // k_spread_order's fallback lists (cluster / region positions)
-  int32_t* d_fba = nullptr;                     // k_region_a_order's fallback list
-  std::vector<int32_t> sets_cls, l_sets;
-  std::vector<SetsArgs> sets_args;
-  SetsArgs* d_sets_args = nullptr;
-  int64_t *d_sets_off = nullptr, *d_sets_scratch = nullptr;
-  uint32_t* d_sets_ovf = nullptr;  // [sets_cls] per component-set class: overflowing rank + 1, or 0
-  int32_t* d_sets_list = nullptr;
-  std::string err;  // packing error text
-  int32_t *d_all = nullptr, *d_cluster = nullptr, *d_region = nullptr, *d_slowlist = nullptr, *d_cs = nullptr;
-  int32_t *status = nullptr, *errc = nullptr, *slow = nullptr;
-  int64_t* arg = nullptr;
-  uint64_t* start = nullptr;
-  uint32_t* count = nullptr;
-  unsigned long long* counter = nullptr;
-  uint32_t* stats = nullptr;
-  unsigned long long* dbg = nullptr;
-  // launch arguments of the kernels that read them through a pointer (kp_launch.h
-  // SelectExtra::dargs): kArgSlots device slots and their page-locked host staging
-  KArgs* d_kargs = nullptr;
-  KArgs* h_kargs = nullptr;
-  size_t h_kargs_bytes = 0;
-  uint32_t h_stats[kStatSlots] = {};  // the counters after a schedule call (KS_*, kp_launch.h)
-  uint32_t* out_idx = nullptr;
-  int32_t* out_rep = nullptr;
-  uint64_t* offsets_d = nullptr;
-  uint64_t* off_part = nullptr;  // per-chunk totals of the offsets scan
-  uint32_t* cidx_d = nullptr;
-  int32_t* crep_d = nullptr;
-  RegionOut* rout = nullptr;
-  int32_t *rstat = nullptr, *rsel = nullptr, *rnsel = nullptr;
-  uint32_t* nhost = nullptr;  // region bindings the device group search left to the host
-  unsigned char* slow_scratch = nullptr;
-  size_t slow_slot = 0;
-  int slow_grid = 0, slow_cap = 0, slow_lds = 0, slow_sort = 0;
-  // k_region_wide: the rows of l_region whose selection can outgrow k_region_b's lists
-  // (cluster MaxGroups > kSmallMax, or a repeated spec.Clusters past kTgtSmallMax), its
-  // own scratch slots (k_slow may run beside it) and LDS sort area; all empty / 0 for a
-  // batch without such bindings, which then launches and allocates nothing for it
-  std::vector<int32_t> l_region_wide;
-  int32_t* d_region_wide = nullptr;
-  unsigned char* wide_scratch = nullptr;
-  size_t wide_slot = 0;
-  int wide_grid = 0, wide_sort = 0;
-  bool fast_ok = false;  // the batch half of the fast pair-kernel condition (batch_fast_ok)
-  int n_regions = 0;     // the snapshot's region count the region buffers were sized for
-  // host results
-  std::vector<int32_t> h_status, h_err, h_rstat, h_rsel, h_rnsel;
-  std::vector<int64_t> h_arg;
-  std::vector<uint64_t> h_start, h_offsets;
-  std::vector<uint32_t> h_count;
-  // result CSR in page-locked host memory (h_res_cap entries each)
-  uint32_t* h_cidx = nullptr;
-  int32_t* h_crep = nullptr;
-  uint64_t h_res_cap = 0;
-  SchedPend pend;         // a submitted call (schedule_submit) awaiting schedule_finish
-  bool sched_done = false;  // h_status holds a completed schedule call's statuses (kp_fit_diagnosis_batch)
-  size_t h_cidx_bytes = 0, h_crep_bytes = 0;  // their pooled block sizes
-  // The packed result form (kp_results_packed), allocated on the batch's first packed call
-  // (ensure_packed): per-binding escape counts [B] and their scan [B + 1] on the device,
-  // the scan's page-locked host copy. The packed words take cidx_d / h_cidx and the
-  // escaped replicas crep_d / h_crep, which a packed call does not otherwise use.
-  uint32_t* wcount_d = nullptr;
-  uint64_t* woff_d = nullptr;
-  uint64_t* h_woff = nullptr;
-  size_t h_woff_bytes = 0;
-  // The batch's device arena and page-locked buffers go back to the process-wide
-  // pools on destruction, where another batch (of any engine) may take them at
-  // once. An entry point that fails part-way leaves kernels queued that still
-  // use them: it records these events on the engine's streams (batch_fence), and
-  // destruction waits for them. kp_batch_create does the same through
-  // create_stream while it runs.
-  dev::event_t fence[3] = {};
-  bool fenced = false;
-  dev::stream_t create_stream = nullptr;
-  void quiesce() {
-    if (create_stream) (void)dev::sync(create_stream);
-    create_stream = nullptr;
-    for (auto& ev : fence)
-      if (ev) {
-        if (fenced) (void)dev::event_sync(ev);
-        dev::event_destroy(ev);
-        ev = nullptr;
-      }
-    fenced = false;
-    if (pend.ev) {  // a submitted call never collected: its work uses the buffers
-      if (pend.live) (void)dev::event_sync(pend.ev);
-      dev::event_destroy(pend.ev);
-      pend.ev = nullptr;
-    }
-    pend.live = false;
-  }
-  ~kp_batch() {
-    quiesce();
-    buf_pool().put(-1, h_cidx, h_cidx_bytes);
-    buf_pool().put(-1, h_crep, h_crep_bytes);
-    buf_pool().put(-1, h_kargs, h_kargs_bytes);
-    buf_pool().put(-1, h_woff, h_woff_bytes);
-    if (est) dev::release(est);
-    if (wcount_d) dev::release(wcount_d);  // (one allocation: woff_d lies behind the counts)
-  }
-  std::vector<RegionOut> h_rout;
-};
+}  // namespace kp::host
 
 int build_sets_args(const kp_snapshot* s, const kp_component* comps, uint32_t K, SetsArgs* A, std::string* err);
 
 // ============================================================================
 // Snapshot packing (cache.Snapshot, cache.go:124-139, packed once)
 // ============================================================================
-namespace {
+namespace kp::host {
 
-typedef std::map<std::string, k8s::Qty> QtyMap;
 bool qmap(const kp_resource* r, uint32_t n, QtyMap* m) {
   bool ok = true;
   for (uint32_t i = 0; i < n; i++) {
@@ -594,6 +45,10 @@ bool qmap(const kp_resource* r, uint32_t n, QtyMap* m) {
   }
   return ok;
 }
+
+}  // namespace kp::host
+
+namespace {
 
 int upload_snapshot(kp_engine* e, kp_snapshot* s);
 int snapshot_est_kind(const kp_snapshot* s);
@@ -1104,6 +559,34 @@ std::atomic<uint64_t> g_pack_cyc[8];
 #define KP_PACK_MARK_INIT
 #define KP_PACK_MARK(i)
 #endif
+}  // namespace
+
+namespace kp::host {
+
+// labels.NewRequirement validation (labels/selector.go:150-230)
+bool valid_req(std::string_view key, std::string_view op, const kp_str* v, uint32_t n) {
+  bool ok = k8s::label_key(key);
+  if (op == "In" || op == "NotIn") ok = ok && n > 0;
+  else if (op == "=") ok = ok && n == 1;
+  else if (op == "Exists" || op == "DoesNotExist") ok = ok && n == 0;
+  else if (op == "Gt" || op == "Lt") {
+    ok = ok && n == 1;
+    for (uint32_t i = 0; i < n; i++) {
+      int64_t x;
+      if (!k8s::parse_int64(SV(v[i]), &x)) ok = false;
+    }
+  } else {
+    ok = false;
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (!k8s::label_value(SV(v[i]))) ok = false;
+  return ok;
+}
+
+}  // namespace kp::host
+
+namespace {
+
 struct Packer {
   kp_snapshot* s;
   Pools* bt;  // this packer's pools (one per packing thread, merged by kp_batch_create)
@@ -1194,25 +677,6 @@ struct Packer {
     i.c = c;
     i.v = v;
     out.push_back(i);
-  }
-  // labels.NewRequirement validation (labels/selector.go:150-230)
-  static bool valid_req(std::string_view key, std::string_view op, const kp_str* v, uint32_t n) {
-    bool ok = k8s::label_key(key);
-    if (op == "In" || op == "NotIn") ok = ok && n > 0;
-    else if (op == "=") ok = ok && n == 1;
-    else if (op == "Exists" || op == "DoesNotExist") ok = ok && n == 0;
-    else if (op == "Gt" || op == "Lt") {
-      ok = ok && n == 1;
-      for (uint32_t i = 0; i < n; i++) {
-        int64_t x;
-        if (!k8s::parse_int64(SV(v[i]), &x)) ok = false;
-      }
-    } else {
-      ok = false;
-    }
-    for (uint32_t i = 0; i < n; i++)
-      if (!k8s::label_value(SV(v[i]))) ok = false;
-    return ok;
   }
   static bool list_ref_a(int32_t op) { return op == OP_EXCLUDE || op == OP_NAMES; }
   static bool list_ref_b(int32_t op) {
@@ -4994,577 +4458,6 @@ static int max_available_replicas_impl(kp_engine* e, kp_batch* bt, uint64_t bind
 int kp_max_available_replicas(kp_engine* e, kp_batch* bt, uint64_t binding, const uint32_t* cluster_idx, uint64_t n,
                               int32_t* out) {
   return batch_fence(e, bt, max_available_replicas_impl(e, bt, binding, cluster_idx, n, out));
-}
-
-// ---------------------------------------------------------------------------
-// Member-cluster nodes
-// ---------------------------------------------------------------------------
-namespace {
-// util.Resource (util/resource.go:28-93): cpu in milli, the rest in units; scalar
-// resources only under IsScalarResourceName.
-struct NodeRes {
-  int64_t cpu = 0, mem = 0, eph = 0, pods = 0;
-  std::map<std::string, int64_t> sc;
-};
-void res_add(NodeRes& r, const QtyMap& rl) {
-  for (auto& kv : rl) {
-    const std::string& n = kv.first;
-    if (n == "cpu") r.cpu += k8s::milli(kv.second);
-    else if (n == "memory") r.mem += k8s::value(kv.second);
-    else if (n == "pods") r.pods += k8s::value(kv.second);
-    else if (n == "ephemeral-storage") r.eph += k8s::value(kv.second);
-    else if (k8s::scalar_resource(n)) r.sc[n] += k8s::value(kv.second);
-  }
-}
-k8s::Qty qty_of(int64_t v, int64_t unit_nano, int fmt) {
-  k8s::Qty q;
-  q.nano = (k8s::i128)v * unit_nano;
-  q.fmt = fmt;
-  return q;
-}
-// getNodeAvailable (cluster_status_controller.go:613-639); false: no pod room
-// (the caller's walk stops there).
-bool node_available(const kp_node& nd, QtyMap* out) {
-  QtyMap alloc;
-  if (!qmap(nd.allocatable, nd.n_allocatable, &alloc)) return false;
-  if (nd.n_pods == 0) {  // no pods on the node: nodePodResourcesMap has no entry
-    *out = alloc;
-    return true;
-  }
-  QtyMap req;
-  qmap(nd.requested, nd.n_requested, &req);
-  NodeRes pr;
-  res_add(pr, req);
-  pr.pods += nd.n_pods;  // AddResourcePods
-  QtyMap al;  // Resource.ResourceList(): the positive fields
-  if (pr.cpu > 0) al["cpu"] = qty_of(pr.cpu, 1000000, 0);
-  if (pr.mem > 0) al["memory"] = qty_of(pr.mem, 1000000000, 1);
-  if (pr.eph > 0) al["ephemeral-storage"] = qty_of(pr.eph, 1000000000, 1);
-  if (pr.pods > 0) al["pods"] = qty_of(pr.pods, 1000000000, 0);
-  for (auto& kv : pr.sc)
-    if (kv.second > 0) al[kv.first] = qty_of(kv.second, 1000000000, kv.first.rfind("hugepages-", 0) == 0 ? 1 : 0);
-  auto pods_of = [](const QtyMap& m) {
-    auto it = m.find("pods");
-    return it == m.end() ? (int64_t)0 : k8s::value(it->second);
-  };
-  if (pods_of(alloc) - pods_of(al) <= 0) return false;
-  for (auto& kv : al) {
-    auto it = alloc.find(kv.first);
-    if (it != alloc.end()) k8s::qsub(it->second, kv.second);
-  }
-  *out = alloc;
-  return true;
-}
-// A member cluster's nodes in one call's dictionary (NodeView's host arrays).
-struct HostNodes {
-  std::vector<uint32_t> flags;
-  std::vector<int32_t> name, lbl_off{0}, tnt_off{0}, tnt;
-  std::vector<int64_t> lbl, lbl_int;
-  std::vector<uint8_t> lbl_int_ok;
-};
-void pack_nodes(const kp_node* nodes, uint64_t n, Dict& d, HostNodes& h) {
-  for (uint64_t i = 0; i < n; i++) {
-    const kp_node& nd = nodes[i];
-    h.flags.push_back(nd.unschedulable ? 1u : 0u);
-    const std::string nm = S(nd.name);
-    h.name.push_back(nm.empty() ? -1 : d.add(nm));
-    std::map<std::string, std::string> lm;  // node.Labels is a map
-    for (uint32_t j = 0; j < nd.n_labels; j++) lm[S(nd.labels[j].key)] = S(nd.labels[j].value);
-    for (auto& kv : lm) {
-      h.lbl.push_back(((int64_t)d.add(kv.first) << 32) | (int64_t)(uint32_t)d.add(kv.second));
-      int64_t x = 0;
-      const bool ok = k8s::parse_int64(kv.second, &x);
-      h.lbl_int.push_back(ok ? x : 0);
-      h.lbl_int_ok.push_back(ok ? 1 : 0);
-    }
-    h.lbl_off.push_back((int32_t)h.lbl.size());
-    for (uint32_t j = 0; j < nd.n_taints; j++) {
-      const std::string ef = S(nd.taints[j].effect);
-      if (ef != "NoSchedule" && ef != "NoExecute") continue;  // DoNotScheduleTaintsFilterFunc
-      h.tnt.push_back(d.add(S(nd.taints[j].key)));
-      h.tnt.push_back(d.add(S(nd.taints[j].value)));
-      h.tnt.push_back(ef == "NoSchedule" ? EFF_NOSCHEDULE : EFF_NOEXECUTE);
-    }
-    h.tnt_off.push_back((int32_t)(h.tnt.size() / 3));
-  }
-}
-// pb.NodeClaim -> ClaimProg's host arrays (offsets relative to this claim).
-struct HostClaim {
-  std::vector<int64_t> sel;
-  std::vector<Tol> tols;
-  int32_t tol_unsched = 0, has_aff = 0;
-  std::vector<int32_t> term_off{0};
-  std::vector<NodeReq> reqs;
-  std::vector<int32_t> vals;
-};
-void compile_claim(const kp_node_claim* c, Dict& d, HostClaim& h) {
-  if (!c) return;
-  std::map<std::string, std::string> sm;  // labels.SelectorFromSet: one requirement per key
-  for (uint32_t j = 0; j < c->n_node_selector; j++) sm[S(c->node_selector[j].key)] = S(c->node_selector[j].value);
-  for (auto& kv : sm) h.sel.push_back(((int64_t)d.add(kv.first) << 32) | (int64_t)(uint32_t)d.add(kv.second));
-  for (uint32_t j = 0; j < c->n_tolerations; j++) {
-    const kp_toleration& t = c->tolerations[j];
-    const std::string ef = S(t.effect), key = S(t.key), op = S(t.op), val = S(t.value);
-    // TolerationsTolerateTaint for {node.kubernetes.io/unschedulable, NoSchedule}
-    if ((ef.empty() || ef == "NoSchedule") && (key.empty() || key == "node.kubernetes.io/unschedulable") &&
-        (op == "Exists" || ((op.empty() || op == "Equal") && val.empty())))
-      h.tol_unsched = 1;
-    Tol x;
-    if (ef.empty()) x.eff = EFF_ANY;
-    else if (ef == "NoSchedule") x.eff = EFF_NOSCHEDULE;
-    else if (ef == "NoExecute") x.eff = EFF_NOEXECUTE;
-    else continue;
-    x.key = key.empty() ? -1 : d.add(key);
-    if (op.empty() || op == "Equal") {
-      x.op = TOL_EQUAL;
-      x.val = d.add(val);
-    } else if (op == "Exists") {
-      x.op = TOL_EXISTS;
-      x.val = -1;
-    } else {
-      continue;  // Lt/Gt disabled, unknown operators never tolerate
-    }
-    h.tols.push_back(x);
-  }
-  // nodeaffinity.NewLazyErrorNodeSelector (nodeaffinity.go:50-67, 155-263): empty
-  // terms select nothing and are dropped; a term with a parse error never matches.
-  h.has_aff = c->has_node_affinity ? 1 : 0;
-  if (!h.has_aff) return;
-  for (uint32_t t = 0; t < c->n_node_affinity_terms; t++) {
-    const kp_node_selector_term& term = c->node_affinity_terms[t];
-    if (term.n_match_expressions == 0 && term.n_match_fields == 0) continue;
-    std::vector<NodeReq> rq;
-    std::vector<int32_t> vl;
-    bool ok = true;
-    for (uint32_t q = 0; q < term.n_match_expressions && ok; q++) {  // nodeSelectorRequirementsAsSelector
-      const kp_requirement& r = term.match_expressions[q];
-      const std::string key = S(r.key), op = S(r.op);
-      if (!(op == "In" || op == "NotIn" || op == "Exists" || op == "DoesNotExist" || op == "Gt" || op == "Lt") ||
-          !Packer::valid_req(key, op, r.values, r.n_values)) {
-        ok = false;
-        break;
-      }
-      NodeReq x{};
-      x.key = d.add(key);
-      if (op == "In" || op == "NotIn") {
-        x.op = op == "In" ? NA_IN : NA_NOTIN;
-        x.voff = (int32_t)(h.vals.size() + vl.size());
-        for (uint32_t j = 0; j < r.n_values; j++) vl.push_back(d.add(S(r.values[j])));
-        x.nv = (int32_t)r.n_values;
-      } else if (op == "Exists" || op == "DoesNotExist") {
-        x.op = op == "Exists" ? NA_EXISTS : NA_DNE;
-      } else {
-        x.op = op == "Gt" ? NA_GT : NA_LT;
-        k8s::parse_int64(S(r.values[0]), &x.x);
-      }
-      rq.push_back(x);
-    }
-    for (uint32_t q = 0; q < term.n_match_fields && ok; q++) {  // nodeSelectorRequirementsAsFieldSelector
-      const kp_requirement& r = term.match_fields[q];
-      const std::string key = S(r.key), op = S(r.op);
-      if (!(op == "In" || op == "NotIn") || r.n_values != 1) {
-        ok = false;
-        break;
-      }
-      const std::string v = S(r.values[0]);
-      NodeReq x{};
-      if (key == "metadata.name") {  // extractNodeFields: the only field a node carries
-        x.op = op == "In" ? NA_NAME_IN : NA_NAME_NOTIN;
-        x.voff = d.add(v);
-      } else {  // fields.Set.Get of an absent field is ""
-        x.op = ((op == "In") == v.empty()) ? NA_FIELD_TRUE : NA_FIELD_FALSE;
-      }
-      rq.push_back(x);
-    }
-    if (!ok) continue;
-    h.reqs.insert(h.reqs.end(), rq.begin(), rq.end());
-    h.vals.insert(h.vals.end(), vl.begin(), vl.end());
-    h.term_off.push_back((int32_t)h.reqs.size());
-  }
-}
-// Device copies of HostNodes and of several claims (one ClaimProg each).
-struct DevNodes {
-  NodeView v{};
-  std::vector<ClaimProg> progs;
-  uint32_t *d_flags = nullptr;
-  int32_t *d_name = nullptr, *d_loff = nullptr, *d_toff = nullptr, *d_tnt = nullptr, *d_toffs = nullptr,
-          *d_vals = nullptr;
-  int64_t *d_lbl = nullptr, *d_lint = nullptr, *d_sel = nullptr;
-  uint8_t* d_lok = nullptr;
-  Tol* d_tols = nullptr;
-  NodeReq* d_reqs = nullptr;
-  std::vector<int64_t> sel;
-  std::vector<Tol> tols;
-  std::vector<int32_t> toffs, vals;
-  std::vector<NodeReq> reqs;
-  std::vector<size_t> o_sel, o_tol, o_toff, o_req, o_val;
-  void plan(Arena& ar, const HostNodes& h, const std::vector<HostClaim>& cl) {
-    for (auto& c : cl) {
-      o_sel.push_back(sel.size());
-      o_tol.push_back(tols.size());
-      o_toff.push_back(toffs.size());
-      o_req.push_back(reqs.size());
-      o_val.push_back(vals.size());
-      sel.insert(sel.end(), c.sel.begin(), c.sel.end());
-      tols.insert(tols.end(), c.tols.begin(), c.tols.end());
-      toffs.insert(toffs.end(), c.term_off.begin(), c.term_off.end());
-      reqs.insert(reqs.end(), c.reqs.begin(), c.reqs.end());
-      vals.insert(vals.end(), c.vals.begin(), c.vals.end());
-    }
-    ar.add(&d_flags, h.flags.data(), h.flags.size(), 1);
-    ar.add(&d_name, h.name.data(), h.name.size(), 1);
-    ar.add(&d_loff, h.lbl_off.data(), h.lbl_off.size());
-    ar.add(&d_lbl, h.lbl.data(), h.lbl.size(), 1);
-    ar.add(&d_lint, h.lbl_int.data(), h.lbl_int.size(), 1);
-    ar.add(&d_lok, h.lbl_int_ok.data(), h.lbl_int_ok.size(), 1);
-    ar.add(&d_toff, h.tnt_off.data(), h.tnt_off.size());
-    ar.add(&d_tnt, h.tnt.data(), h.tnt.size(), 1);
-    ar.add(&d_sel, sel.data(), sel.size(), 1);
-    ar.add(&d_tols, tols.data(), tols.size(), 1);
-    ar.add(&d_toffs, toffs.data(), toffs.size(), 1);
-    ar.add(&d_reqs, reqs.data(), reqs.size(), 1);
-    ar.add(&d_vals, vals.data(), vals.size(), 1);
-  }
-  // (after the arena's alloc()) the node view and each claim's program over the sub-buffers
-  void views(const std::vector<HostClaim>& cl, uint64_t n) {
-    v = NodeView{n, d_flags, d_name, d_loff, d_lbl, d_lint, d_lok, d_toff, d_tnt};
-    for (size_t k = 0; k < cl.size(); k++) {
-      ClaimProg p{};
-      p.sel = d_sel + o_sel[k];
-      p.n_sel = (int32_t)cl[k].sel.size();
-      p.tols = d_tols + o_tol[k];
-      p.n_tols = (int32_t)cl[k].tols.size();
-      p.tol_unsched = cl[k].tol_unsched;
-      p.has_aff = cl[k].has_aff;
-      p.n_terms = (int32_t)cl[k].term_off.size() - 1;
-      p.term_off = d_toffs + o_toff[k];
-      p.reqs = d_reqs + o_req[k];
-      p.vals = d_vals + o_val[k];
-      progs.push_back(p);
-    }
-  }
-};
-void split128(k8s::i128 v, int64_t* hi, uint64_t* lo) {
-  *hi = (int64_t)(v >> 64);
-  *lo = (uint64_t)v;
-}
-}  // namespace
-
-int kp_model_grades(kp_engine* e, const kp_resource_model* models, uint32_t n_models, const kp_node* nodes,
-                    uint64_t n_nodes, int64_t* out_counts) {
-  if (!e || (n_models && !models) || (n_nodes && !nodes) || (n_models && !out_counts)) return KP_EINVAL;
-  (void)dev::set_device(e->device);
-  if (n_models == 0) return KP_OK;  // getAllocatableModelings returns nil
-  // modeling.InitSummary (modeling.go:75-102)
-  std::vector<std::string> rs_name;
-  std::vector<QtyMap> rs_list;
-  for (uint32_t g = 0; g < n_models; g++) {
-    QtyMap tmp;
-    for (uint32_t j = 0; j < models[g].n_ranges; j++) {
-      const kp_model_range& it = models[g].ranges[j];
-      if (rs_name.size() != models[g].n_ranges) rs_name.push_back(S(it.name));
-      k8s::Qty q;
-      if (!k8s::parse_quantity(S(it.min), &q)) {
-        e->err = "kp_model_grades: unparsable range minimum";
-        return KP_EINVAL;
-      }
-      tmp[S(it.name)] = q;
-    }
-    rs_list.push_back(tmp);
-  }
-  if (!rs_name.empty() && rs_name.size() != rs_list[0].size()) {
-    e->err = "the number of resourceName is not equal the number of resourceList";
-    return KP_EINVAL;
-  }
-  if (rs_name.empty()) {  // getIndex would index RMs[MaxInt]
-    e->err = "kp_model_grades: resource models without ranges";
-    return KP_EINVAL;
-  }
-  const int K = (int)n_models, NR = (int)rs_name.size();
-  std::vector<int64_t> mh((size_t)NR * K), vh;
-  std::vector<uint64_t> ml((size_t)NR * K), vl;
-  for (int r = 0; r < NR; r++)
-    for (int g = 0; g < K; g++) {
-      auto it = rs_list[g].find(rs_name[r]);
-      split128(it == rs_list[g].end() ? (k8s::i128)0 : it->second.nano, &mh[(size_t)r * K + g], &ml[(size_t)r * K + g]);
-    }
-  // the nodes' available resources, up to the first without pod room
-  uint64_t n = 0;
-  vh.reserve((size_t)n_nodes * NR);
-  vl.reserve((size_t)n_nodes * NR);
-  for (; n < n_nodes; n++) {
-    QtyMap av;
-    if (!node_available(nodes[n], &av)) break;
-    for (int r = 0; r < NR; r++) {
-      auto it = av.find(rs_name[r]);
-      int64_t h;
-      uint64_t l;
-      split128(it == av.end() ? (k8s::i128)0 : it->second.nano, &h, &l);
-      vh.push_back(h);
-      vl.push_back(l);
-    }
-  }
-  Arena a;
-  int64_t *d_mh, *d_vh;
-  uint64_t *d_ml, *d_vl;
-  unsigned long long* d_cnt;
-  a.add(&d_mh, mh.data(), mh.size());
-  a.add(&d_ml, ml.data(), ml.size());
-  a.add(&d_vh, vh.data(), vh.size(), 1);
-  a.add(&d_vl, vl.data(), vl.size(), 1);
-  a.add(&d_cnt, K);
-  HIPCHK(a.alloc());
-  dev::stream_t st = e->stream;
-  HIPCHK(a.upload(st));
-  HIPCHK(dev::fill(d_cnt, 0, 8 * (size_t)K, st));
-  GradesArgs A{K, NR, d_mh, d_ml, d_vh, d_vl, n, d_cnt};
-  HIPCHK(dev::grades(st, A));
-  std::vector<unsigned long long> c(K);
-  HIPCHK(dev::d2h(c.data(), d_cnt, 8 * (size_t)K, st));
-  HIPCHK(dev::sync(st));
-  for (int g = 0; g < K; g++) out_counts[g] = (int64_t)c[g];
-  return KP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// One estimator-server call over a member cluster's nodes: the slots of every
-// resource the components (and the Estimate request) name, the nodes' available
-// resources in those slots, and a ClaimProg per component (+ the request's claim).
-struct NodeJob {
-  std::vector<std::string> slot{"pods"};
-  NodeSetsArgs A{};
-  std::vector<int64_t> avail;
-  std::vector<uint32_t> present;
-  Dict d;
-  HostNodes hn;
-  std::vector<HostClaim> cl;
-  std::string err;
-  int rc = KP_OK;
-  static bool divides(const std::string& nm) {
-    return nm == "cpu" || nm == "memory" || nm == "ephemeral-storage" || k8s::scalar_resource(nm);
-  }
-  static int64_t field(const NodeRes& r, const std::string& nm, bool* present) {
-    *present = true;
-    if (nm == "pods") return r.pods;
-    if (nm == "cpu") return r.cpu;
-    if (nm == "memory") return r.mem;
-    if (nm == "ephemeral-storage") return r.eph;
-    auto it = r.sc.find(nm);
-    *present = it != r.sc.end();
-    return *present ? it->second : 0;
-  }
-  int fail(int code, const char* m) {
-    rc = code;
-    err = m;
-    return code;
-  }
-  // phases: the assumed workloads (empty ones skipped), then `main` (may be empty).
-  int build(const kp_node* nodes, uint64_t n, const kp_assumed_workload* assumed, uint32_t n_assumed,
-            const kp_node_component* main, uint32_t K, const QtyMap* extra) {
-    std::vector<const kp_node_component*> comps;
-    A.n = n;
-    A.mono = 1;
-    A.n_phase = 0;
-    for (uint32_t w = 0; w < n_assumed; w++) {
-      if (assumed[w].n_components == 0) continue;  // noderesource.go:168-170
-      if (assumed[w].n_components > (uint32_t)kNodeComp || A.n_phase + 1 >= kNodePhase)
-        return fail(KP_ENOTSUP, "more than 16 assumed workloads or 16 components in one");
-      A.ph_k0[A.n_phase++] = (int32_t)comps.size();
-      for (uint32_t k = 0; k < assumed[w].n_components; k++) comps.push_back(&assumed[w].components[k]);
-    }
-    if (K) {
-      A.ph_k0[A.n_phase++] = (int32_t)comps.size();
-      for (uint32_t k = 0; k < K; k++) comps.push_back(&main[k]);
-    }
-    A.ph_k0[A.n_phase] = (int32_t)comps.size();
-    A.last_upper = K ? INT32_MAX : 1;
-    if (comps.size() > (size_t)kNodeCompAll) return fail(KP_ENOTSUP, "more than 64 components in all");
-    std::vector<NodeRes> creq(comps.size());
-    for (size_t k = 0; k < comps.size(); k++) {
-      const kp_node_component& c = *comps[k];
-      if (!c.has_replica_requirements) continue;
-      QtyMap q;
-      if (!qmap(c.resource_request, c.n_resource_request, &q)) return fail(KP_EINVAL, "unparsable resource request");
-      res_add(creq[k], q);
-      for (auto& kv : q)
-        if (divides(kv.first) && std::find(slot.begin(), slot.end(), kv.first) == slot.end()) slot.push_back(kv.first);
-    }
-    if (extra)
-      for (auto& kv : *extra)
-        if (divides(kv.first) && std::find(slot.begin(), slot.end(), kv.first) == slot.end()) slot.push_back(kv.first);
-    if (slot.size() > (size_t)kNodeRes) return fail(KP_ENOTSUP, "more than 7 distinct requested resources");
-    A.NU = (int32_t)slot.size();
-    for (size_t k = 0; k < comps.size(); k++) {
-      A.replicas[k] = comps[k]->replicas;
-      if (comps[k]->replicas < 0) A.mono = 0;
-      for (int u = 0; u < A.NU; u++) {
-        bool pr;
-        const int64_t v = u == 0 ? 1 : field(creq[k], slot[u], &pr);
-        A.req[k][u] = v;
-        A.pos[k][u] = v > 0 ? v : 0;
-        if (v < 0) A.mono = 0;
-      }
-    }
-    // getNodesAvailableResources / getNodeAvailableResource (noderesource.go:135-144,205-220)
-    avail.assign((size_t)n * A.NU, 0);
-    present.assign(n, 0);
-    for (uint64_t i = 0; i < n; i++) {
-      const kp_node& nd = nodes[i];
-      QtyMap al, rqd;
-      if (!qmap(nd.allocatable, nd.n_allocatable, &al) || !qmap(nd.requested, nd.n_requested, &rqd))
-        return fail(KP_EINVAL, "unparsable node quantity");
-      NodeRes a, r;
-      res_add(a, al);
-      res_add(r, rqd);
-      uint32_t pm = 0;
-      for (int u = 0; u < A.NU; u++) {
-        bool pa, prq;
-        const int64_t va = field(a, slot[u], &pa), vr = field(r, slot[u], &prq);
-        int64_t x = 0;
-        if (u == 0) x = std::max<int64_t>(std::max<int64_t>(va - vr, 0) - (int64_t)nd.n_pods, 0);
-        else if (pa) x = prq ? std::max<int64_t>(va - vr, 0) : va;  // SubResource: absent scalars stay absent
-        avail[(size_t)i * A.NU + u] = x;
-        if (pa) pm |= 1u << u;
-      }
-      present[i] = pm;
-    }
-    A.max_steps = A.mono ? 4 * (int64_t)comps.size() * ((int64_t)n + 2) + 64 : (int64_t)1 << 20;
-    pack_nodes(nodes, n, d, hn);
-    cl.resize(comps.size());
-    for (size_t k = 0; k < comps.size(); k++)
-      if (comps[k]->has_replica_requirements) compile_claim(comps[k]->node_claim, d, cl[k]);
-    return KP_OK;
-  }
-};
-}  // namespace
-
-extern "C" {
-
-// Runs the job's set phases on the device; *sets = the last phase's count. On
-// return the job's node state (d_avail) holds the deducted resources.
-static int node_job_run(kp_engine* e, NodeJob& J, const kp_node_claim* est_claim, NodeEstArgs* est, int32_t* sets) {
-  Arena ar;
-  DevNodes dn;
-  if (est) J.cl.emplace_back(), compile_claim(est_claim, J.d, J.cl.back());
-  dn.plan(ar, J.hn, J.cl);
-  const size_t NP = J.cl.size();
-  const int KS = J.A.ph_k0[J.A.n_phase];
-  ClaimProg* d_progs;
-  NodeSetsArgs* d_args;
-  int64_t* d_avail;
-  uint32_t *d_present, *d_ovf, *d_sum;
-  uint8_t* d_match;
-  int32_t* d_out;
-  ar.add(&d_progs, std::max<size_t>(1, NP));
-  ar.add(&d_args, 1);
-  ar.add(&d_avail, J.avail.data(), J.avail.size(), 1);
-  ar.add(&d_present, J.present.data(), J.present.size(), 1);
-  ar.add(&d_match, std::max<size_t>(1, (size_t)KS * J.A.n));
-  ar.add(&d_out, 1);
-  ar.add(&d_ovf, 1);
-  ar.add(&d_sum, 1);
-  HIPCHK(ar.alloc());
-  dev::stream_t st = e->stream;
-  HIPCHK(ar.upload(st));
-  dn.views(J.cl, J.A.n);
-  J.A.avail = d_avail;
-  J.A.present = d_present;
-  J.A.match = d_match;
-  J.A.out = d_out;
-  J.A.ovf = d_ovf;
-  // (the claim programs and the arguments hold device pointers, known after alloc(): direct copies)
-  if (NP) HIPCHK(dev::h2d(d_progs, dn.progs.data(), sizeof(ClaimProg) * NP, st));
-  HIPCHK(dev::h2d(d_args, &J.A, sizeof(J.A), st));
-  HIPCHK(dev::fill(d_out, 0, 4, st));
-  HIPCHK(dev::fill(d_ovf, 0, 4, st));
-  if (KS > 0 && J.A.n > 0) {
-    HIPCHK(dev::node_match(st, dn.v, d_progs, KS, d_match));
-    HIPCHK(dev::node_sets(st, d_args));
-  }
-  if (est) {
-    HIPCHK(dev::fill(d_sum, 0, 4, st));
-    est->v = dn.v;
-    est->p = dn.progs.back();
-    est->NU = J.A.NU;
-    est->avail = d_avail;
-    est->sum = d_sum;
-    HIPCHK(dev::node_est(st, *est));
-  }
-  int32_t res = 0;
-  uint32_t ovf = 0, sum = 0;
-  HIPCHK(dev::d2h(&res, d_out, 4, st));
-  HIPCHK(dev::d2h(&ovf, d_ovf, 4, st));
-  if (est) HIPCHK(dev::d2h(&sum, d_sum, 4, st));
-  HIPCHK(dev::sync(st));
-  if (ovf) {
-    e->err = "the first-fit simulation exceeded its step bound";
-    return KP_ENOTSUP;
-  }
-  *sets = est ? (int32_t)sum : res;
-  return KP_OK;
-}
-
-int kp_node_max_replicas(kp_engine* e, const kp_node* nodes, uint64_t n_nodes, const kp_resource* request,
-                         uint32_t n_request, const kp_node_claim* claim, const kp_assumed_workload* assumed,
-                         uint32_t n_assumed, int32_t* out) {
-  if (!e || !out || (n_nodes && !nodes) || (n_request && !request) || (n_assumed && !assumed)) return KP_EINVAL;
-  (void)dev::set_device(e->device);
-  *out = 0;
-  QtyMap rq;
-  if (!qmap(request, n_request, &rq)) {
-    e->err = "kp_node_max_replicas: unparsable resource request";
-    return KP_EINVAL;
-  }
-  if (n_nodes == 0) return KP_OK;  // estimate.go:43-45
-  NodeJob J;
-  if (J.build(nodes, n_nodes, assumed, n_assumed, nullptr, 0, &rq) != KP_OK) {
-    e->err = "kp_node_max_replicas: " + J.err;
-    return J.rc;
-  }
-  // MaxDivided's dividing entries (resource.go:221-248): cpu milli, memory,
-  // ephemeral-storage, scalar resources, each > 0
-  NodeEstArgs E{};
-  for (auto& kv : rq) {
-    const std::string& nm = kv.first;
-    if (!NodeJob::divides(nm)) continue;
-    const int64_t v = nm == "cpu" ? k8s::milli(kv.second) : k8s::value(kv.second);
-    const int u = (int)(std::find(J.slot.begin(), J.slot.end(), nm) - J.slot.begin());
-    if (v > 0) E.q[u] = v;
-  }
-  int32_t sum = 0;
-  const int rc = node_job_run(e, J, claim, &E, &sum);
-  if (rc != KP_OK) return rc;
-  *out = sum;
-  return KP_OK;
-}
-
-int kp_node_max_component_sets(kp_engine* e, const kp_node* nodes, uint64_t n_nodes,
-                               const kp_node_component* comps, uint32_t K, const kp_assumed_workload* assumed,
-                               uint32_t n_assumed, int32_t* out) {
-  if (!e || !out || (n_nodes && !nodes) || (K && !comps) || (n_assumed && !assumed)) return KP_EINVAL;
-  (void)dev::set_device(e->device);
-  *out = 0;
-  if (K == 0) {  // noNodeConstraint (noderesource.go:155-158)
-    *out = INT32_MAX;
-    return KP_OK;
-  }
-  if (K > (uint32_t)kNodeComp) {
-    e->err = "kp_node_max_component_sets: more than 16 components";
-    return KP_ENOTSUP;
-  }
-  NodeJob J;
-  if (J.build(nodes, n_nodes, assumed, n_assumed, comps, K, nullptr) != KP_OK) {
-    e->err = "kp_node_max_component_sets: " + J.err;
-    return J.rc;
-  }
-  if (n_nodes == 0) return KP_OK;  // no node holds a set
-  int32_t sets = 0;
-  const int rc = node_job_run(e, J, nullptr, nullptr, &sets);
-  if (rc != KP_OK) return rc;
-  *out = sets;
-  return KP_OK;
 }
 
 int kp_last_stage_times(const kp_engine* e, kp_stage_times* out) {

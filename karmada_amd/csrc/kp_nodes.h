@@ -1,7 +1,7 @@
 // kp_nodes.h — member-cluster node kernels: the resource-model
 // grade histogram (modeling.AddToResourceSummary) and the accurate estimator's
 // per-node MaxDivided sum (noderesource.nodeResourceEstimator.Estimate). The host
-// (engine.cpp) resolves names and exact Quantities; the device classifies and
+// (nodes.cpp) resolves names and exact Quantities; the device classifies and
 // divides one node per thread.
 #pragma once
 #include "kp_layout.h"

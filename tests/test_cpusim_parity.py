@@ -1,4 +1,4 @@
-"""CPU parity of the engine's own code: libkp_cpusim.so runs engine.cpp and the
+"""CPU parity of the engine's own code: libkp_cpusim.so runs the host units and the
 kernel bodies of kp_kernels.h (1-thread block policy) on the host, checked
 against the oracle. The GPU build of the same bodies is checked in
 tests/test_gpu_parity.py; this file keeps the logic covered on every CPU run."""

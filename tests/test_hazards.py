@@ -2,7 +2,7 @@
 hazard H5, the pkg/util/binding_test.go tables (GetSumOfReplicas, MergeTargetClusters,
 RescheduleRequired), and a one-binding batch whose serial result list is checked
 against the batch's result pool (sink_serial). The engine side runs through
-libkp_cpusim.so (engine.cpp + the kernel bodies on the host); the GPU build of the
+libkp_cpusim.so (the host units + the kernel bodies on the host); the GPU build of the
 same universes is checked in tests/test_gpu_parity.py."""
 import ctypes as C
 import json

@@ -1,6 +1,6 @@
 // driver.cpp — sanitizer run of the engine's host code (test infrastructure).
 //
-// Builds engine.cpp + dev_cpu.cpp (the kernel bodies on host threads: the CPU-sim
+// Builds the host units + dev_cpu.cpp (the kernel bodies on host threads: the CPU-sim
 // device layer), the synthetic universes (synth.cpp) and the oracle (oracle.cpp)
 // into one program, instrumented with ThreadSanitizer or AddressSanitizer +
 // UndefinedBehaviorSanitizer (tools/sanitize/Makefile). It schedules seeded

@@ -11,5 +11,6 @@ objs=""
 for t in 1 2 3 4 5 6 7 8 9 10 11 12 13; do
   if [ $t = $tu ]; then objs="$objs kernels_v${name}_tu$t.o"; else objs="$objs kernels_tu$t.o"; fi
 done
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libkp_$name.so $objs engine.o multi.o -lpthread
+for u in $(make -s print-units); do objs="$objs $u.o"; done
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libkp_$name.so $objs multi.o -lpthread
 echo "built karmada_amd/libkp_$name.so"
