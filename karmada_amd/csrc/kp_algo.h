@@ -513,7 +513,7 @@ KP_UNROLL
 // Fast != EST_GENERIC: the launch guarantees md != nullptr (zero past n_tmpl),
 // the dense node-count matrix (n_tmpl <= kTmplDense, every template value >= 0
 // so every MaxDivided is >= 0), every sreq_cnt <= kReqUnroll and every divisor
-// <= 2^60 (pair_fast_ok, engine.cpp), so the cold fallbacks are compiled out.
+// <= 2^60 (pair_fast_ok: snapshot.cpp, pack.cpp), so the cold fallbacks are compiled out.
 template <int Fast = EST_GENERIC>
 KP_HD inline int32_t est_compute(const SnapView& s, const BatchView& bv, const BindHdr& h, int c, const int32_t* md,
                                  const EstOps& o) {

@@ -1,4 +1,4 @@
-// kp_dev.h — the device interface the host units (engine.cpp, nodes.cpp) run on.
+// kp_dev.h — the device interface the host units (engine.cpp, snapshot.cpp, pack.cpp, nodes.cpp) run on.
 //
 // libkp.so implements it with HIP on gfx950 (kernels.hip). The test-only
 // libkp_cpusim.so implements it on the host (dev_cpu.cpp) by running the same

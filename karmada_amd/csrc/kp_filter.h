@@ -5,7 +5,7 @@
 // predicates, and every predicate a binding can state is a union / intersection /
 // complement of a few snapshot-wide cluster sets: the clusters carrying label k=v,
 // provider p, region r or zone z, enabling GVK g, holding taint list t, not being
-// deleted. upload_snapshot (engine.cpp) stores each of those sets once as a
+// deleted. upload_snapshot (snapshot.cpp) stores each of those sets once as a
 // W-word bitset row (SnapView::bits); a binding's feasibility word w is then the
 // same boolean expression over word w of the rows its selector names. One wave64
 // per binding, one lane per word: a binding costs O(rows named x W / 64) word

@@ -296,11 +296,17 @@ struct NoInitAlloc : std::allocator<T> {
   }
 };
 
-// The helpers that cross a unit boundary (engine.cpp defines them, nodes.cpp calls them):
-// a resource list as quantities, and the labels.NewRequirement validation.
+// The helpers that cross a unit boundary, each defined in one unit: a resource list as
+// quantities (snapshot.cpp defines it; engine.cpp and nodes.cpp call it too), the
+// labels.NewRequirement validation (pack.cpp; nodes.cpp), and from engine.cpp the MaxDivided
+// table entries per workgroup (snapshot.cpp), the batch's LDS check and a component list
+// resolved against the snapshot (pack.cpp).
 typedef std::map<std::string, k8s::Qty> QtyMap;
 bool qmap(const kp_resource* r, uint32_t n, QtyMap* m);
 bool valid_req(std::string_view key, std::string_view op, const kp_str* v, uint32_t n);
+int md_cap_of(const kp_snapshot* s);
+int batch_lds_check(kp_engine* e, const kp_snapshot* s, const kp_batch* bt);
+int build_sets_args(const kp_snapshot* s, const kp_component* comps, uint32_t K, SetsArgs* A, std::string* err);
 
 }  // namespace kp::host
 using namespace kp::host;

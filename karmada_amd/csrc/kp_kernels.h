@@ -210,7 +210,7 @@ KP_UNROLL
 }
 
 // Fast: the estimator instance (EST_*, kp_algo.h); every instance but
-// EST_GENERIC needs pair_fast_ok (engine.cpp): est_mode 0, the MaxDivided and
+// EST_GENERIC needs pair_fast_ok (snapshot.cpp, pack.cpp): est_mode 0, the MaxDivided and
 // taint-set tables in LDS, no cold fallbacks.
 template <int Fast, class BLK>
 KP_FI void pair_one(const BLK& B, int b, unsigned char* smem, const SnapView& s, const BatchView& bv, uint64_t* fmask,

@@ -1,6 +1,6 @@
 // nodes.cpp — the node estimator: a member cluster's nodes and claims compiled for the
 // device, kp_model_grades, kp_node_max_replicas and kp_node_max_component_sets. Needs
-// qmap and valid_req (engine.cpp).
+// qmap (snapshot.cpp) and valid_req (pack.cpp).
 #include "kp_host.h"
 #include "kp_nodes.h"
 

@@ -186,7 +186,7 @@ def test_refusal_above_ceiling_gpu(gpu_engine, config):
 
 # ---- the class-order switch -------------------------------------------------------------
 def check_order_switch(engine, config, n_clusters):
-    """engine.cpp builds no class orders above C = 16 384 (with_orders): the launch set
+    """pack.cpp builds no class orders above C = 16 384 (with_orders): the launch set
     changes between 16 384 and 16 385, the placements do not."""
     u = synth.Universe(config, SEED, n_clusters, 0, N_BINDINGS)
     # (a batch builds class orders when each serves KP_ORDER_AMORT bindings, 4 by default;
