@@ -283,7 +283,8 @@ typedef struct kp_options {
    * kp_schedule_batch, kp_schedule_affinities and kp_multi_schedule return
    * KP_ENOTSUP for a snapshot with n_out_of_tree_plugins > 0, except that a batch
    * holding those plugins' filter verdicts (kp_batch_create_filters, filter-only
-   * plugins, n_plugins equal to this count) schedules. The per-pair entry
+   * plugins, n_plugins equal to this count) schedules, and so does
+   * kp_schedule_affinities_ex with such answers. The per-pair entry
    * points (kp_filter_reasons, kp_score_batch, kp_max_available_replicas) still
    * answer for the in-tree set, for the framework to combine with the others. */
   uint32_t n_out_of_tree_plugins;
@@ -551,8 +552,8 @@ typedef struct kp_estimates {
  * below -1.
  * The per-pair entry points on such a batch (kp_max_available_replicas, kp_filter_*,
  * kp_score_batch) keep answering for the in-tree set only: kp_max_available_replicas is
- * the GeneralEstimator's answer, not the merged one. kp_schedule_affinities and kp_multi_*
- * do not take estimates. */
+ * the GeneralEstimator's answer, not the merged one. kp_schedule_affinities takes estimates
+ * through kp_schedule_affinities_ex; kp_multi_* does not take them. */
 int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
                               const kp_binding_key* keys /* may be NULL */, uint64_t n_bindings,
                               kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
@@ -593,8 +594,8 @@ typedef struct kp_filter_answers {
  * the gate: plugins registered, none objected). Bits at or above n_clusters in a row's last word are ignored.
  * KP_EINVAL (kp_last_error says which) when n_clusters differs from the snapshot's cluster
  * count, rows is null, row_of is null with n_bindings > 0, a row_of entry is outside
- * -1..n_rows-1, or n_rows > 0 with n_plugins == 0. kp_schedule_affinities and kp_multi_*
- * take no answers. */
+ * -1..n_rows-1, or n_rows > 0 with n_plugins == 0. kp_schedule_affinities takes answers
+ * through kp_schedule_affinities_ex; kp_multi_* takes none. */
 int kp_batch_create_filters(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings,
                             const kp_binding_key* keys /* may be NULL */, uint64_t n_bindings,
                             kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
@@ -639,6 +640,34 @@ int kp_results_unpack(const kp_results_packed* in, uint32_t* cluster_idx, int32_
  * without ClusterAffinities run once (scheduleResourceBinding, scheduler.go:584-600). */
 int kp_schedule_affinities(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n_bindings,
                            kp_affinity_results* out);
+
+/* The estimators' answers and the out-of-tree filter plugins' verdicts for the retry loop.
+ * An estimator reads the request, not the term, so est->row_of has one entry per binding as
+ * in kp_batch_create_estimates. A filter plugin sees the spec with the current term's
+ * affinity substituted (scheduler.go:630-640), so its verdict may differ from term to term:
+ * flt->row_of has one entry per (binding, term), found through term_off. */
+typedef struct kp_affinity_answers {
+  const kp_estimates* est;      /* may be NULL; row_of has n_bindings entries */
+  const kp_filter_answers* flt; /* may be NULL; rows / n_rows / n_clusters / n_plugins as in
+                                   kp_batch_create_filters, row_of per (binding, term) */
+  const uint64_t* term_off;     /* n_bindings + 1 entries when flt has rows: binding i's verdict rows are
+                                   flt->row_of[term_off[i] + t], t = 0 .. max(1, n_cluster_affinities) - 1 */
+} kp_affinity_answers;
+/* kp_schedule_affinities with answers: every round's batch merges them as a
+ * kp_batch_create_filters batch does, a binding's verdict row being that of the term it is
+ * trying. The error kept when every term fails is that of the first attempted term as the
+ * answered batch reports it: a FitError where the row rejects what the in-tree set passes,
+ * KP_ERR_* with the capacity the estimates reduce. The rows are uploaded once per call and
+ * brought into cluster rank order on the device; each round's batch borrows them. The call
+ * runs when (flt ? flt->n_plugins : 0) equals the snapshot's n_out_of_tree_plugins (a flt
+ * with n_rows == 0 still states its n_plugins) and returns KP_ENOTSUP otherwise. ans == NULL,
+ * answers without rows and row_of entries all -1 give kp_schedule_affinities' results, and
+ * nothing is allocated, uploaded or launched for them. KP_EINVAL (kp_last_error says which)
+ * under the rules of kp_batch_create_estimates and kp_batch_create_filters, and when flt has
+ * rows and term_off is null, is not non-decreasing, or term_off[i + 1] - term_off[i] differs
+ * from max(1, n_cluster_affinities) of binding i. Nothing is retained after the call. */
+int kp_schedule_affinities_ex(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n_bindings,
+                              const kp_affinity_answers* ans /* may be NULL */, kp_affinity_results* out);
 
 /* FilterPlugin boundary: feasibility of every (binding, cluster) pair after
  * RunFilterPlugins (+ the skip-deleting rule of findClustersThatFit).

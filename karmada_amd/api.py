@@ -219,6 +219,9 @@ def estimates(rows, row_of):
     return e, (r, ro)
 
 
+_estimates = estimates  # (for functions whose parameter has that name)
+
+
 class kp_filter_answers(C.Structure):
     _fields_ = [("n_rows", u32), ("n_clusters", u64), ("rows", C.POINTER(u64)), ("row_of", C.POINTER(i32)),
                 ("n_plugins", u32)]
@@ -276,6 +279,44 @@ def binding_keys(bindings, n, generations):
 class kp_affinity_results(C.Structure):
     _fields_ = [("results", kp_results), ("affinity_index", C.POINTER(i32)), ("attempts", C.POINTER(i32)),
                 ("rounds", C.c_uint32)]
+
+
+class kp_affinity_answers(C.Structure):
+    _fields_ = [("est", C.POINTER(kp_estimates)), ("flt", C.POINTER(kp_filter_answers)), ("term_off", C.POINTER(u64))]
+
+
+def affinity_answers(n_terms, estimates=None, filters=None, n_clusters=None):
+    """kp_affinity_answers for kp_schedule_affinities_ex. n_terms: max(1, n_cluster_affinities)
+    per binding. estimates = (rows, row_of) as for `estimates`. filters = (rows, row_of,
+    n_plugins) as for `filter_answers`, except that row_of holds a list per binding: its row
+    id for each of its terms (one entry for a binding without ClusterAffinities). Returns the
+    struct and what it points into (keep it alive for the call)."""
+    import numpy as np
+    ans = kp_affinity_answers()
+    keep = []
+    if estimates is not None:
+        rows, row_of = estimates
+        if len(row_of) != len(n_terms):
+            raise ValueError(f"estimates: row_of has {len(row_of)} entries for {len(n_terms)} bindings")
+        e, k = _estimates(rows, row_of)
+        keep += [e, k]
+        ans.est = C.pointer(e)
+    if filters is not None:
+        rows, row_of, n_plugins = filters
+        if len(row_of) != len(n_terms):
+            raise ValueError(f"filters: row_of has {len(row_of)} lists for {len(n_terms)} bindings")
+        flat = []
+        for i, (ro, t) in enumerate(zip(row_of, n_terms)):
+            if len(ro) != t:
+                raise ValueError(f"filters: binding {i} has {t} term(s) and {len(ro)} row ids")
+            flat += [int(x) for x in ro]
+        f, k = filter_answers(rows, flat, n_plugins, n_clusters)
+        off = np.zeros(len(n_terms) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(np.asarray(n_terms, dtype=np.uint64))
+        keep += [f, k, off]
+        ans.flt = C.pointer(f)
+        ans.term_off = off.ctypes.data_as(C.POINTER(u64))
+    return ans, keep
 
 
 class kp_kernel_time(C.Structure):

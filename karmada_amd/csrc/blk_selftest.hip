@@ -1,6 +1,7 @@
 // blk_selftest.hip — test-only library (libkp_blktest.so): checks every GpuBlk
 // primitive (kp_blk.h) on the device against a host computation, for several
-// workgroup sizes and seeded random inputs. Never linked into libkp.so.
+// workgroup sizes and seeded random inputs; and runs the row-ranking kernel bodies of
+// kp_kernels.h over caller-given rows. Never linked into libkp.so.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include "kp_blk.h"
 #include "kp_pdq.h"
 #include "kp_select.h"
+#include "kp_kernels.h"
 
 using namespace kp;
 
@@ -303,4 +305,63 @@ extern "C" int kp_webster_reg_selftest(const int64_t* votes, const int32_t* offs
   int declined = 0;
   for (int j = 0; j < nl; j++) declined += ok[j] ? 0 : 1;
   return declined;
+}
+
+// The two row-ranking kernels of kp_schedule_affinities_ex (kp_kernels.h body_est_rows_rank,
+// body_flt_rows_rank) over caller-given rows and permutation, with the launch shapes of
+// kernels.hip (gpu != 0) or on the host block (gpu == 0): est_src[n_est][C] ->
+// est_dst[n_est][Cp], flt_src[n_flt][ceil(C/64)] -> flt_dst[n_flt][Cp/64]; perm has Cp
+// entries. Returns 0, or -1 on a HIP error.
+extern "C" __global__ void __launch_bounds__(256) k_est_rows_rank_test(int C, int Cp, const uint32_t* perm,
+                                                                     const int32_t* src, int32_t* dst) {
+  body_est_rows_rank(GpuBlk{nullptr}, (int)blockIdx.x, C, Cp, perm, src, dst);
+}
+extern "C" __global__ void __launch_bounds__(256) k_flt_rows_rank_test(int n_rows, int C, int W, const uint32_t* perm,
+                                                                     const uint64_t* src, uint64_t* dst) {
+  const int i = (int)(blockIdx.x * 4) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n_rows * W) return;
+  body_flt_rows_rank(GpuBlk{nullptr}, i / W, i % W, C, W, perm, src, dst);
+}
+
+extern "C" int kp_rows_rank_selftest(int gpu, int C, int Cp, const uint32_t* perm, const int32_t* est_src, int n_est,
+                                     int32_t* est_dst, const uint64_t* flt_src, int n_flt, uint64_t* flt_dst,
+                                     char* msg, int msg_len) {
+  const int W = Cp / 64, Wc = (C + 63) / 64;
+  if (!gpu) {
+    for (int r = 0; r < n_est; r++) body_est_rows_rank(CpuBlk{nullptr}, r, C, Cp, perm, est_src, est_dst);
+    for (int i = 0; i < n_flt * W; i++) body_flt_rows_rank(CpuBlk{nullptr}, i / W, i % W, C, W, perm, flt_src, flt_dst);
+    return 0;
+  }
+  uint32_t* dp;
+  int32_t *des, *ded;
+  uint64_t *dfs, *dfd;
+  const size_t es = 4 * (size_t)n_est * C, ed = 4 * (size_t)n_est * Cp, fs = 8 * (size_t)n_flt * Wc,
+               fd = 8 * (size_t)n_flt * W;
+  if (hipMalloc(&dp, 4 * (size_t)Cp) || hipMalloc(&des, es + 4) || hipMalloc(&ded, ed + 4) || hipMalloc(&dfs, fs + 8) ||
+      hipMalloc(&dfd, fd + 8)) {
+    snprintf(msg, msg_len, "hipMalloc failed");
+    return -1;
+  }
+  (void)hipMemcpy(dp, perm, 4 * (size_t)Cp, hipMemcpyHostToDevice);
+  (void)hipMemcpy(des, est_src, es, hipMemcpyHostToDevice);
+  (void)hipMemcpy(dfs, flt_src, fs, hipMemcpyHostToDevice);
+  (void)hipMemset(ded, 0xA5, ed);
+  (void)hipMemset(dfd, 0xA5, fd);
+  if (n_est > 0) hipLaunchKernelGGL(k_est_rows_rank_test, dim3(n_est), dim3(256), 0, 0, C, Cp, dp, des, ded);
+  if (n_flt > 0 && W > 0)
+    hipLaunchKernelGGL(k_flt_rows_rank_test, dim3((n_flt * W + 3) / 4), dim3(256), 0, 0, n_flt, C, W, dp, dfs, dfd);
+  int rc = 0;
+  if (hipDeviceSynchronize() != hipSuccess) {
+    snprintf(msg, msg_len, "kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  } else {
+    (void)hipMemcpy(est_dst, ded, ed, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(flt_dst, dfd, fd, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dp);
+  (void)hipFree(des);
+  (void)hipFree(ded);
+  (void)hipFree(dfs);
+  (void)hipFree(dfd);
+  return rc;
 }

@@ -322,6 +322,19 @@ int est_extra(stream_t, int Cp, const int32_t* list, int n, const int32_t* bcls,
   });
 }
 
+int est_rows_rank(stream_t, const SnapView& s, const int32_t* src, int n_rows, int32_t* dst) {
+  return grid("k_est_rows_rank", n_rows, 0, [&](int blk, unsigned char* sm) {
+    body_est_rows_rank(CpuBlk{(int64_t*)sm}, blk, s.C, s.Cp, s.perm, src, dst);
+  });
+}
+
+int flt_rows_rank(stream_t, const SnapView& s, const uint64_t* src, int n_rows, uint64_t* dst) {
+  if (s.W <= 0) return 0;
+  return grid("k_flt_rows_rank", n_rows * s.W, 0, [&](int i, unsigned char* sm) {
+    body_flt_rows_rank(CpuBlk{(int64_t*)sm}, i / s.W, i % s.W, s.C, s.W, s.perm, src, dst);
+  });
+}
+
 int grades(stream_t, const GradesArgs& A) {
   for (uint64_t i = 0; i < A.n; i++) body_grades(A, i);
   return 0;

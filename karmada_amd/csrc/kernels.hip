@@ -447,6 +447,31 @@ extern "C" __global__ void __launch_bounds__(256) k_est_extra(int Cp, const int3
 #else
 ;
 #endif
+// kp_schedule_affinities_ex: a call's answer rows from caller order into rank order. One
+// estimate row per blockIdx.x (4 bytes per lane on the store side, the gather through perm
+// on the load side); one wave64 per (verdict row, 64-cluster word), kFilterWaves per
+// workgroup, the item index through a scalar register as k_filter.
+extern "C" __global__ void __launch_bounds__(256) k_est_rows_rank(int C, int Cp, const uint32_t* perm,
+                                                                const int32_t* src, int32_t* dst)
+#if KP_K(1)
+{
+  body_est_rows_rank(GpuBlk{nullptr}, (int)blockIdx.x, C, Cp, perm, src, dst);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_flt_rows_rank(int n_rows, int C, int W,
+                                                                              const uint32_t* perm,
+                                                                              const uint64_t* src, uint64_t* dst)
+#if KP_K(1)
+{
+  const int i = (int)(blockIdx.x * kFilterWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (i >= n_rows * W) return;  // wave-uniform
+  body_flt_rows_rank(GpuBlk{nullptr}, i / W, i % W, C, W, perm, src, dst);
+}
+#else
+;
+#endif
 extern "C" __global__ void __launch_bounds__(256) k_grades(GradesArgs A)
 #if KP_K(8)
 {
@@ -943,6 +968,21 @@ int est_extra(stream_t st, int Cp, const int32_t* list, int n, const int32_t* bc
   // (a workgroup covers 1024 entries a step; at most 64 along a row, which then stride)
   const int parts = std::max(1, std::min(64, (Cp / 4 + 255) / 256));
   hipLaunchKernelGGL(k_est_extra, dim3(n, parts), dim3(256), 0, (hipStream_t)st, Cp, list, bcls, cls_est, extra, rows);
+  return chk(hipGetLastError());
+}
+
+int est_rows_rank(stream_t st, const SnapView& s, const int32_t* src, int n_rows, int32_t* dst) {
+  if (n_rows <= 0) return 0;
+  hipLaunchKernelGGL(k_est_rows_rank, dim3(n_rows), dim3(256), 0, (hipStream_t)st, s.C, s.Cp, s.perm, src, dst);
+  return chk(hipGetLastError());
+}
+
+int flt_rows_rank(stream_t st, const SnapView& s, const uint64_t* src, int n_rows, uint64_t* dst) {
+  if (n_rows <= 0 || s.W <= 0) return 0;
+  const int64_t items = (int64_t)n_rows * s.W;
+  if (items > INT32_MAX) return chk(hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_flt_rows_rank, dim3((unsigned)((items + kFilterWaves - 1) / kFilterWaves)),
+                     dim3(64 * kFilterWaves), 0, (hipStream_t)st, n_rows, s.C, s.W, s.perm, src, dst);
   return chk(hipGetLastError());
 }
 

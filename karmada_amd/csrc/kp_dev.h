@@ -118,6 +118,11 @@ int rows_from_class(stream_t st, const SnapView& s, const BatchView& bv, const i
 // order, -1 = no answer; negative cls_est: the row is left alone).
 int est_extra(stream_t st, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
               const int32_t* extra, int32_t* rows);
+// kp_schedule_affinities_ex: a call's answer rows, uploaded in caller cluster order, into rank
+// order (body_est_rows_rank, body_flt_rows_rank). src[n_rows][C] -> dst[n_rows][Cp] with -1
+// in the padding; src[n_rows][ceil(C/64)] -> dst[n_rows][W] words with zero bits there.
+int est_rows_rank(stream_t st, const SnapView& s, const int32_t* src, int n_rows, int32_t* dst);
+int flt_rows_rank(stream_t st, const SnapView& s, const uint64_t* src, int n_rows, uint64_t* dst);
 // kp_model_grades: A.counts[grade] += 1 per node (body_grades); A's arrays in device memory.
 int grades(stream_t st, const GradesArgs& A);
 // kp_node_max_replicas: *A.sum += int32 sum of node_replicas over the nodes (wrapping).

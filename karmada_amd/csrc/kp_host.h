@@ -465,6 +465,10 @@ struct kp_batch {
   FltPair* d_flt_list = nullptr;
   uint64_t* d_flt_rows = nullptr;
   uint32_t flt_plugins = 0;
+  // false: d_est_rows / d_flt_rows are lent by a call that made them for several batches
+  // (kp_schedule_affinities_ex, one batch a round): they lie outside this batch's arena, and
+  // the lender frees them after its last batch is destroyed.
+  bool owns_rows = true;
   // component-set classes (BF_SETS): class id and resolved component list of each;
   // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
   // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)
@@ -575,4 +579,19 @@ struct kp_batch {
   }
   std::vector<RegionOut> h_rout;
 };
+
+// kp_batch_create_filters for a batch that borrows its rows (pack.cpp; kp_schedule_affinities_ex
+// calls it once a round): the rows are on the device already, in rank order with their
+// padding ([..][Cp] of -1, [..][W] of zero bits), checked by the lender. est_row_of: the
+// n bindings' estimate rows (null: none); flt_list: the bindings that have a verdict row, in
+// binding order (taken over). The batch neither copies nor frees the rows.
+struct LentRows {
+  const int32_t* est_row_of = nullptr;
+  int32_t* d_est_rows = nullptr;
+  std::vector<FltPair> flt_list;
+  uint64_t* d_flt_rows = nullptr;
+  uint32_t flt_plugins = 0;
+};
+int batch_create_lent(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n, LentRows* lent,
+                      kp_batch** out);
 

@@ -389,6 +389,39 @@ KP_FI void body_reasons_extra(const BLK& B, int i, int C, int W, const FltPair* 
     if ((o[c] & 0xffu) == 0u && !((x[c >> 6] >> (c & 63)) & 1)) o[c] = 8u;
 }
 
+// kp_schedule_affinities_ex uploads its answers' rows once, in caller cluster order, and these
+// two bring them into rank order on the device for every round's batch to borrow (perm:
+// SnapView::perm, rank -> caller index, Cp entries).
+// Estimate row blk: dst[blk][rank] = src[blk][perm[rank]] for rank < C, -1 (no answer) in the
+// padding [C, Cp). The store side is coalesced (4 bytes per lane), the gather is on the load.
+template <class BLK>
+KP_FI void body_est_rows_rank(const BLK& B, int blk, int C, int Cp, const uint32_t* perm, const int32_t* src,
+                              int32_t* dst) {
+  const int32_t* x = src + (size_t)blk * C;
+  int32_t* row = dst + (size_t)blk * Cp;
+  for (int k = B.tid(); k < Cp; k += B.nth()) row[k] = k < C ? x[perm[k]] : -1;
+}
+// Verdict word w of row r by the calling wave: lane l tests caller bit perm[64 w + l] of
+// src[r] (ceil(C / 64) words a row), false at or beyond C, and one ballot is the word of
+// dst[r] ([..][W]), stored by lane 0 (on the host build one "lane" takes the 64 in turn).
+template <class BLK>
+KP_FI void body_flt_rows_rank(const BLK& B, int r, int w, int C, int W, const uint32_t* perm, const uint64_t* src,
+                              uint64_t* dst) {
+  const uint64_t* x = src + (size_t)r * ((C + 63) / 64);
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  uint64_t word = 0;
+  for (int l0 = 0; l0 < 64; l0 += ww) {
+    const int k = 64 * w + l0 + lane;
+    bool bit = false;
+    if (k < C) {
+      const uint32_t cl = perm[k];
+      bit = (x[cl >> 6] >> (cl & 63)) & 1;
+    }
+    word |= B.wballot(bit) << l0;
+  }
+  if (lane == 0) dst[(size_t)r * W + w] = word;
+}
+
 // Pair stage for binding list[b0 + blk] (b0 + blk without a list): each wave evaluates 64 consecutive clusters
 // (coalesced SoA columns), stores their feasibility as one u64 word and
 // calAvailableReplicas per cluster. est_mode 1: raw GeneralEstimator answers for

@@ -1372,7 +1372,8 @@ static int64_t order_amort() {  // (read per batch: tests switch it)
 
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
                              const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est = nullptr, const kp_filter_answers* flt = nullptr);
+                             const kp_estimates* est = nullptr, const kp_filter_answers* flt = nullptr,
+                             LentRows* lent = nullptr);
 int kp_batch_create_filters(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                             uint64_t n, kp_pack_cache* cache, const kp_estimates* est, const kp_filter_answers* flt,
                             kp_batch** out) {
@@ -1441,6 +1442,7 @@ struct CreateCtx {
   uint64_t n;
   const kp_estimates* est;         // null once found empty
   const kp_filter_answers* flt;    // null once found empty
+  LentRows* lent;                  // rows the batch borrows instead (est and flt null), or null
   kp_batch* bt = nullptr;
   std::vector<int32_t> est_rows;   // kp_estimates rows by cluster rank, [n_rows][Cp]
   std::vector<uint64_t> flt_rows;  // kp_filter_answers rows by cluster rank, [n_rows][W]
@@ -1805,14 +1807,18 @@ static int plan_arena(CreateCtx& c) {
   if (!bt->l_est_cls.empty()) {
     a.add(&bt->d_cls_est, bt->cls_est.data(), bt->cls_est.size());
     a.add(&bt->d_est_cls, bt->l_est_cls.data(), bt->l_est_cls.size());
-    a.add(&bt->d_est_rows, c.est_rows.data(), c.est_rows.size());
+    if (bt->owns_rows) a.add(&bt->d_est_rows, c.est_rows.data(), c.est_rows.size());
   }
   if (!bt->l_flt.empty()) {
     a.add(&bt->d_flt_list, bt->l_flt.data(), bt->l_flt.size());
-    a.add(&bt->d_flt_rows, c.flt_rows.data(), c.flt_rows.size());
+    if (bt->owns_rows) a.add(&bt->d_flt_rows, c.flt_rows.data(), c.flt_rows.size());
   }
   c.tp1 = std::chrono::steady_clock::now();
   HIPCHK(a.alloc());
+  if (!bt->owns_rows) {  // (outside the arena: ~kp_batch leaves them to the lender)
+    bt->d_est_rows = c.lent->d_est_rows;
+    bt->d_flt_rows = c.lent->d_flt_rows;
+  }
   bt->h_kargs = (KArgs*)pinned_get(sizeof(KArgs) * kArgSlots, &bt->h_kargs_bytes);
   if (!bt->h_kargs) {
     e->err = "kp_batch_create: page-locked launch-argument slots";
@@ -1853,11 +1859,11 @@ static int upload(CreateCtx& c) {
 // sees: estimates, filters, the components check, then the packer.
 static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
                              const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est, const kp_filter_answers* flt) {
+                             const kp_estimates* est, const kp_filter_answers* flt, LentRows* lent) {
   if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
   if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
   (void)dev::set_device(e->device);
-  CreateCtx c{e, const_cast<kp_snapshot*>(sc), bindings, n, est, flt};
+  CreateCtx c{e, const_cast<kp_snapshot*>(sc), bindings, n, est, flt, lent};
   kp_snapshot* s = c.s;
   if (int rc = take_estimates(c)) return rc;
   if (int rc = take_filters(c)) return rc;
@@ -1869,6 +1875,13 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   bt->hdr.resize(n);
   bt->flt_plugins = c.flt_plugins;
   bt->l_flt = std::move(c.flt_list);
+  const int32_t* est_row_of = c.est ? c.est->row_of : nullptr;
+  if (lent) {
+    bt->owns_rows = false;
+    bt->flt_plugins = lent->flt_plugins;
+    bt->l_flt = std::move(lent->flt_list);
+    est_row_of = lent->est_row_of;
+  }
   c.tp0 = std::chrono::steady_clock::now();
   if (s->opts.multiple_pod_templates_scheduling)
     for (uint64_t i = 0; i < n; i++)
@@ -1877,7 +1890,7 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
                  " has n_components > 0 but no components (the MultiplePodTemplatesScheduling gate reads them)";
         return KP_EINVAL;
       }
-  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache, c.est ? c.est->row_of : nullptr)) {
+  if (!pack_parallel(s, bindings, (int)n, bt, keys, cache, est_row_of)) {
     e->err = bt->err.empty() ? "batch pools exceed 2^31 entries" : bt->err;
     return KP_ENOTSUP;
   }
@@ -1893,3 +1906,8 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
 void kp_batch_destroy(kp_batch* b) { delete b; }
 
 }  // extern "C"
+
+int batch_create_lent(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n, LentRows* lent,
+                      kp_batch** out) {
+  return batch_create_impl(e, sc, bindings, n, nullptr, nullptr, out, nullptr, nullptr, lent);
+}

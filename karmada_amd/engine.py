@@ -37,7 +37,7 @@ EXPORTS = (
     "kp_pack_cache_get_stats",
     "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
     "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
-    "kp_schedule_affinities", "kp_filter_batch", "kp_filter_reasons", "kp_fit_diagnosis_batch", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
+    "kp_schedule_affinities", "kp_schedule_affinities_ex", "kp_filter_batch", "kp_filter_reasons", "kp_fit_diagnosis_batch", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
     "kp_multi_create", "kp_multi_destroy", "kp_multi_last_error", "kp_multi_devices", "kp_multi_engine",
@@ -92,6 +92,8 @@ def load_library(path: str = LIB_PATH):
     L.kp_results_unpack.argtypes = [C.POINTER(api.kp_results_packed), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.kp_schedule_affinities.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64,
                                          C.POINTER(api.kp_affinity_results)]
+    L.kp_schedule_affinities_ex.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64,
+                                            C.POINTER(api.kp_affinity_answers), C.POINTER(api.kp_affinity_results)]
     L.kp_filter_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     L.kp_score_batch.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.kp_filter_reasons.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
@@ -629,24 +631,41 @@ class GenericScheduler:
         b.close()
         return out
 
-    def schedule_affinities_raw(self, structs):
-        """kp_schedule_affinities over packed kp_binding structs: (results dicts, affinity_index, attempts, rounds)."""
+    def schedule_affinities_raw(self, structs, estimates=None, filters=None):
+        """kp_schedule_affinities over packed kp_binding structs: (results dicts, affinity_index, attempts, rounds).
+        With `estimates` = (rows, row_of) as for Batch and / or `filters` = (rows, row_of, n_plugins), row_of
+        holding a list per binding with one row id per term, it is kp_schedule_affinities_ex."""
         ba, n = structs
         eng = self.snapshot.engine
         r = api.kp_affinity_results()
-        eng._check(eng.L.kp_schedule_affinities(eng.h, self.snapshot.h, ba, n, C.byref(r)), "kp_schedule_affinities")
+        if estimates is None and filters is None:
+            eng._check(eng.L.kp_schedule_affinities(eng.h, self.snapshot.h, ba, n, C.byref(r)), "kp_schedule_affinities")
+        else:
+            n_terms = [max(1, int(ba[i].n_cluster_affinities)) for i in range(n)]
+            ans, keep = api.affinity_answers(n_terms, estimates, filters, len(self.snapshot.names))
+            eng._check(eng.L.kp_schedule_affinities_ex(eng.h, self.snapshot.h, ba, n, C.byref(ans), C.byref(r)),
+                       "kp_schedule_affinities_ex")
+            del keep
         rr = r.results
         res = api.results_to_python(rr.status, rr.err_code, rr.err_arg, rr.offsets, rr.cluster_idx, rr.replicas,
                                     rr.n_bindings)
         return res, [int(r.affinity_index[i]) for i in range(n)], [int(r.attempts[i]) for i in range(n)], r.rounds
 
     def schedule_with_affinities(self, bindings: Sequence[dict]) -> List[ScheduleResult]:
+        """schedule_affinities without answers."""
+        return self.schedule_affinities(bindings)
+
+    def schedule_affinities(self, bindings: Sequence[dict], estimates=None, filters=None) -> List[ScheduleResult]:
         """Scheduler.scheduleResourceBindingWithClusterAffinities (scheduler.go:618-684) per binding,
         batched: every term retry of a round runs as one device batch. Each result carries the
-        AffinityName that became Status.SchedulerObservedAffinityName (None: unchanged)."""
+        AffinityName that became Status.SchedulerObservedAffinityName (None: unchanged).
+        estimates: (rows, row_of), the scheduler-estimator's answers as for Batch. filters:
+        (rows, row_of, n_plugins), the out-of-tree filter plugins' verdicts, row_of[i] a list
+        with binding i's row id for each of its terms (one entry without ClusterAffinities):
+        a plugin sees the spec with the term's affinity substituted."""
         w = api.World()
         structs = w.bindings(bindings)
-        res, aff, _, _ = self.schedule_affinities_raw(structs)
+        res, aff, _, _ = self.schedule_affinities_raw(structs, estimates, filters)
         names = self.snapshot.names
         out = []
         for b, r, a in zip(bindings, res, aff):

@@ -36,7 +36,7 @@ import json
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 from karmada_amd import api
-from karmada_amd.engine import Batch, PackCache, Snapshot
+from karmada_amd.engine import Batch, GenericScheduler, PackCache, Snapshot
 
 SUCCESS, UNSCHEDULABLE, ERROR = 0, 1, 2  # framework.Code (interface.go:124-133)
 
@@ -383,8 +383,9 @@ class Shim:
     The batch path refuses a registry with out-of-tree filter/score plugins
     (kp_options.n_out_of_tree_plugins, KP_ENOTSUP) unless all of them are filter-only and
     given as `filter_plugins` (instances, registry order): schedule_batch then runs them once
-    per distinct binding class and hands their verdicts in (kp_batch_create_filters). The
-    per-pair answers stay available either way.
+    per distinct binding class and hands their verdicts in (kp_batch_create_filters), and
+    schedule_affinities does the same per (binding, term) for the ClusterAffinities retry
+    loop (kp_schedule_affinities_ex). The per-pair answers stay available either way.
     """
 
     def __init__(self, engine, clusters: Sequence[dict], opts: Optional[api.kp_options] = None,
@@ -433,6 +434,35 @@ class Shim:
         view = self._view(specs, generations)
         self._register(view, specs)
         return view.batch.schedule()
+
+    def schedule_affinities(self, specs: Sequence[dict], estimates=None):
+        """scheduleResourceBindingWithClusterAffinities for every spec (kp_schedule_affinities_ex),
+        under the batch path's condition: every out-of-tree plugin filter-only and given as
+        `filter_plugins`. They run once per distinct class of (spec with the term's affinity
+        substituted, scheduler.go:630-640) and cluster, so a spec has a verdict row per term.
+        estimates: (rows, row_of), the scheduler-estimator's answers as for engine.Batch.
+        Returns engine.ScheduleResult per spec (with observed_affinity_name)."""
+        filters = None
+        if self.filter_plugins:
+            per_term, n_terms = [], []
+            for sp in specs:
+                placement = sp.get("placement") or {}
+                terms = placement.get("clusterAffinities") or []
+                n_terms.append(max(1, len(terms)))
+                for t in terms:
+                    aff = {k: v for k, v in t.items() if k != "affinityName"}
+                    per_term.append(dict(sp, placement=dict(placement, clusterAffinity=aff),
+                                         schedulerObservedAffinityName=t.get("affinityName")))
+                if not terms:
+                    per_term.append(sp)
+            answers = FilterAnswers(self.filter_plugins, per_term, self.clusters, self.class_key)
+            flat, row_of = iter(answers.row_of), []
+            for t in n_terms:
+                row_of.append([next(flat) for _ in range(t)])
+            filters = (answers.rows, row_of, answers.n_plugins)
+        gs = GenericScheduler.__new__(GenericScheduler)
+        gs.snapshot = self.snap
+        return gs.schedule_affinities(list(specs), estimates=estimates, filters=filters)
 
     def slot_of(self, spec: dict) -> Tuple[BatchView, int]:
         hit = self.by.get(id(spec))

@@ -10,6 +10,7 @@
 // synthetic universes lack (several affinity terms, a list of more than 64 values,
 // more than four tolerations, spec.Clusters members with eviction tasks) through
 // the bitset filter, every (binding, cluster) pair against the oracle's filter.
+// run_affinity_answers runs kp_schedule_affinities_ex with both answers (borrowed rows).
 // Exit code 0 = no mismatch (the sanitizers abort on their own findings).
 #include <algorithm>
 #include <cstdio>
@@ -361,6 +362,102 @@ static int run_filter_shapes(kp_engine* e) {
   return bad ? 1 : 0;
 }
 
+// kp_schedule_affinities_ex with both answers over a universe with multi-term bindings: the
+// rows go up once and every round's batch borrows them, so the sanitizer sees them freed
+// exactly once (a second free or a leak aborts the run). Three calls: rows that change
+// nothing (the oracle's retry driver is the reference); rows that reject everything on each
+// binding's first term and halve the estimates, so that later rounds run on borrowed rows;
+// and a call whose first round's batch creation fails (a binding with n_components > 0 and
+// no components under the MultiplePodTemplatesScheduling gate) after the rows were made.
+static int run_affinity_answers(kp_engine* e) {
+  kps_world* w = nullptr;
+  const uint32_t C = 150;
+  if (kps_create(6, 6, C, 0, 600, &w)) return 1;
+  uint64_t nc = 0, nb = 0;
+  const kp_cluster* cl = kps_clusters(w, &nc);
+  const kp_binding* bs = kps_bindings(w, &nb);
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  o.n_out_of_tree_plugins = 1;
+  const uint64_t wc = (nc + 63) / 64;
+  std::vector<uint64_t> term_off(nb + 1, 0);
+  for (uint64_t i = 0; i < nb; i++) term_off[i + 1] = term_off[i] + std::max<uint32_t>(1, bs[i].n_cluster_affinities);
+  std::vector<int32_t> erows(2 * nc, INT32_MAX), erow_of(nb), frow_of(term_off[nb]);
+  std::fill(erows.begin() + (long)nc, erows.end(), -1);
+  for (uint64_t i = 0; i < nb; i++) erow_of[i] = (int32_t)(i % 3) - 1;
+  std::vector<uint64_t> frows(2 * wc, ~0ull);  // row 0: all pass (stray bits above C); row 1: none passes
+  std::fill(frows.begin() + (long)wc, frows.end(), 0ull);
+  for (uint64_t k = 0; k < frow_of.size(); k++) frow_of[k] = (int32_t)(k % 2) - 1;  // -1 or the all-ones row
+  const kp_estimates est{2, nc, erows.data(), erow_of.data()};
+  const kp_filter_answers flt{2, nc, frows.data(), frow_of.data(), 1};
+  const kp_affinity_answers ans{&est, &flt, term_off.data()};
+  kp_snapshot* s = nullptr;
+  kp_affinity_results r{};
+  int bad = 0;
+  uint64_t retried = 0;
+  if (kp_snapshot_create(e, cl, nc, &o, &s) || kp_schedule_affinities_ex(e, s, bs, nb, &ans, &r)) {
+    fprintf(stderr, "affinity answers: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  } else {
+    kp_options o0 = o;
+    o0.n_out_of_tree_plugins = 0;
+    kpo_world* ow = kpo_world_create(cl, nc, &o0);
+    kpo_results* want = nullptr;
+    std::vector<int32_t> widx(nb), watt(nb);
+    kpo_schedule_affinities(ow, bs, nb, KPO_FAST, 4, &want, widx.data(), watt.data());
+    for (uint64_t i = 0; i < nb; i++) {
+      const bool same = r.results.status[i] == want->status[i] && r.results.err_code[i] == want->err_code[i] &&
+                        r.results.err_arg[i] == want->err_arg[i] && r.affinity_index[i] == widx[i] &&
+                        r.attempts[i] == watt[i] &&
+                        targets_of(r.results.offsets, r.results.cluster_idx, r.results.replicas, i) ==
+                            targets_of(want->offsets, want->cluster_idx, want->replicas, i);
+      if (!same && bad++ < 3) fprintf(stderr, "affinity answers: binding %llu differs\n", (unsigned long long)i);
+    }
+    kpo_results_free(want);
+    kpo_world_destroy(ow);
+    // every binding's first term rejected, the later ones not; small estimates
+    std::fill(erows.begin(), erows.begin() + (long)nc, 1);
+    for (uint64_t i = 0; i < nb; i++)
+      for (uint64_t k = term_off[i]; k < term_off[i + 1]; k++) frow_of[k] = k == term_off[i] ? 1 : -1;
+    if (kp_schedule_affinities_ex(e, s, bs, nb, &ans, &r)) {
+      fprintf(stderr, "affinity answers: rejecting rows: engine error: %s\n", kp_last_error(e));
+      bad++;
+    } else {
+      for (uint64_t i = 0; i < nb; i++) {
+        // (a binding that resumes at a later term, or reschedules, starts where its rows allow)
+        if (bs[i].n_cluster_affinities == 0 && r.results.status[i] != KP_STATUS_FIT_ERROR && bad++ < 3)
+          fprintf(stderr, "affinity answers: binding %llu without terms passed an all-zero row\n", (unsigned long long)i);
+        retried += r.attempts[i] >= 2;
+      }
+      if (r.rounds < 2 || retried == 0) bad++;
+    }
+  }
+  if (s) kp_snapshot_destroy(s);
+  // a round whose batch creation fails: the rows are up already and must go with the call
+  {
+    kp_options om = o;
+    om.multiple_pod_templates_scheduling = 1;
+    std::vector<kp_binding> broken(bs, bs + nb);
+    broken[nb / 2].n_components = 1;
+    broken[nb / 2].components = nullptr;
+    kp_snapshot* sm = nullptr;
+    if (kp_snapshot_create(e, cl, nc, &om, &sm)) {
+      bad++;
+    } else {
+      const int rc = kp_schedule_affinities_ex(e, sm, broken.data(), nb, &ans, &r);
+      if (rc != KP_EINVAL && bad++ < 3) fprintf(stderr, "affinity answers: the broken binding gave rc %d\n", rc);
+      // the engine is usable afterwards, with the same rows
+      if (kp_schedule_affinities_ex(e, sm, bs, nb, &ans, &r)) bad++;
+    }
+    if (sm) kp_snapshot_destroy(sm);
+  }
+  kps_destroy(w);
+  printf("affinity answers: %llu bindings x %u clusters, %llu retried under rejecting rows, %d mismatches\n",
+         (unsigned long long)nb, C, (unsigned long long)retried, bad);
+  return bad ? 1 : 0;
+}
+
 // `driver ceiling`: the snapshots at which a workgroup's LDS is full (tests/test_lds_ceiling.py:
 // 18 624 clusters without spread bindings, 14 336 with them, and the class-order switch at
 // 16 384 / 16 385) instead of the small universes, so the sanitizer sees every global array
@@ -380,6 +477,7 @@ int main(int argc, char** argv) {
              {3, 5, 16384, 100, false},  {10, 5, 16385, 100, false}, {7, 5, 16385, 100, false}};
   for (auto& c : cases) fails += run_case(e, std::get<0>(c), std::get<1>(c), std::get<2>(c), std::get<3>(c), std::get<4>(c));
   if (!ceiling) fails += run_filter_shapes(e);
+  if (!ceiling) fails += run_affinity_answers(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
