@@ -1682,57 +1682,30 @@ static uint32_t affinity_index_of(const kp_binding& b) {
   return 0;
 }
 
-// kp_affinity_answers checked as kp_batch_create_estimates / _filters check theirs (n_clusters,
-// null arrays, the row_of ranges, a row value below -1, rows without plugins), with the
-// filter row_of indexed through term_off: one entry per (binding, term).
+// kp_affinity_answers checked by the shared intake (kp_host.h), with the rules of term_off,
+// which the verdicts' row_of is indexed through (one entry per binding and term), here.
 static int check_affinity_answers(kp_engine* e, const kp_snapshot* s, const kp_binding* bs, uint64_t n,
                                   const kp_estimates* est, const kp_filter_answers* flt, const uint64_t* term_off) {
+  const char* who = "kp_schedule_affinities_ex";
   auto bad = [&](const std::string& why) {
-    e->err = "kp_schedule_affinities_ex: " + why;
+    e->err = std::string(who) + ": " + why;
     return KP_EINVAL;
   };
-  auto clusters = [&](const char* what, uint64_t n_clusters) {
-    return std::string(what) + "->n_clusters is " + std::to_string(n_clusters) + ", the snapshot holds " +
-           std::to_string(s->C) + " clusters";
-  };
-  auto outside = [&](const char* what, uint64_t k, int32_t v, uint32_t n_rows) {
-    return std::string(what) + "->row_of[" + std::to_string(k) + "] = " + std::to_string(v) + " is outside -1.." +
-           std::to_string((int64_t)n_rows - 1);
-  };
-  if (est && est->n_rows) {
-    if (est->n_clusters != (uint64_t)s->C) return bad(clusters("est", est->n_clusters));
-    if (!est->rows || (n && !est->row_of)) return bad("est->rows or est->row_of is null");
-    if (est->n_rows > (uint32_t)INT32_MAX) return bad("est: more than 2^31 - 1 rows");
-    for (uint64_t i = 0; i < n; i++)
-      if (est->row_of[i] < -1 || est->row_of[i] >= (int64_t)est->n_rows)
-        return bad(outside("est", i, est->row_of[i], est->n_rows));
-    const size_t cells = (size_t)est->n_rows * s->C;
-    for (size_t k = 0; k < cells; k++)
-      if (est->rows[k] < -1)
-        return bad("est->rows[" + std::to_string(k / s->C) + "][" + std::to_string(k % s->C) + "] = " +
-                   std::to_string(est->rows[k]) + " is below -1 (UnauthenticReplica)");
-  }
-  if (flt && flt->n_rows) {
-    if (flt->n_clusters != (uint64_t)s->C) return bad(clusters("flt", flt->n_clusters));
-    if (!flt->rows) return bad("flt->rows is null");
-    if (n && !flt->row_of) return bad("flt->row_of is null");
-    if (flt->n_plugins == 0) return bad("flt->n_rows is " + std::to_string(flt->n_rows) + " with n_plugins == 0");
-    if (flt->n_rows > (uint32_t)INT32_MAX) return bad("flt: more than 2^31 - 1 rows");
-    if (!term_off) return bad("term_off is null while flt has rows");
-    for (uint64_t i = 0; i < n; i++)
-      if (term_off[i + 1] < term_off[i])
-        return bad("term_off is not non-decreasing: term_off[" + std::to_string(i + 1) + "] is below term_off[" +
-                   std::to_string(i) + "]");
-    for (uint64_t i = 0; i < n; i++) {
-      const uint64_t terms = std::max<uint32_t>(1, bs[i].n_cluster_affinities);
-      if (term_off[i + 1] - term_off[i] != terms)
-        return bad("term_off[" + std::to_string(i + 1) + "] - term_off[" + std::to_string(i) + "] is " +
-                   std::to_string(term_off[i + 1] - term_off[i]) + ", binding " + std::to_string(i) + " has " +
-                   std::to_string(terms) + " term(s) (max(1, n_cluster_affinities))");
-      for (uint64_t k = term_off[i]; k < term_off[i + 1]; k++)
-        if (flt->row_of[k] < -1 || flt->row_of[k] >= (int64_t)flt->n_rows)
-          return bad(outside("flt", k, flt->row_of[k], flt->n_rows));
-    }
+  if (int rc = check_estimates(e, s, who, "est->", est, n)) return rc;
+  if (int rc = check_filters(e, s, who, "flt->", flt, n)) return rc;
+  if (!flt || flt->n_rows == 0) return KP_OK;
+  if (!term_off) return bad("term_off is null while flt has rows");
+  for (uint64_t i = 0; i < n; i++)
+    if (term_off[i + 1] < term_off[i])
+      return bad("term_off is not non-decreasing: term_off[" + std::to_string(i + 1) + "] is below term_off[" +
+                 std::to_string(i) + "]");
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t terms = std::max<uint32_t>(1, bs[i].n_cluster_affinities);
+    if (term_off[i + 1] - term_off[i] != terms)
+      return bad("term_off[" + std::to_string(i + 1) + "] - term_off[" + std::to_string(i) + "] is " +
+                 std::to_string(term_off[i + 1] - term_off[i]) + ", binding " + std::to_string(i) + " has " +
+                 std::to_string(terms) + " term(s) (max(1, n_cluster_affinities))");
+    if (int rc = check_row_of(e, who, "flt->", flt->row_of, term_off[i], terms, flt->n_rows)) return rc;
   }
   return KP_OK;
 }
@@ -1759,39 +1732,24 @@ int kp_schedule_affinities_ex(kp_engine* e, const kp_snapshot* s, const kp_bindi
   };
   if (est && !(est->n_rows && used(est->row_of, n))) est = nullptr;
   if (flt && !(flt->n_rows && n && used(flt->row_of + term_off[0], term_off[n] - term_off[0]))) flt = nullptr;
-  // The rows go up once, in caller cluster order, and come into rank order on the device;
-  // every round's batch borrows them. `rows` outlives those batches and frees both row sets
-  // with the staging copies when the call returns, whichever way.
-  const bool lend = est || flt || flt_plugins;
-  Arena rows;
-  int32_t *d_est_src = nullptr, *d_est_rows = nullptr;
-  uint64_t *d_flt_src = nullptr, *d_flt_rows = nullptr;
+  // The rows go up once and come into rank order on the device; every round's batch shares
+  // them, and they go back to the pool with the last holder, whichever way the call returns.
+  std::shared_ptr<const AnswerRows> rows;
   if (est || flt) {
     (void)dev::set_device(e->device);
-    const size_t Wc = ((size_t)s->C + 63) / 64;
-    if (est) {
-      rows.add(&d_est_src, est->rows, (size_t)est->n_rows * s->C);
-      rows.add(&d_est_rows, (size_t)est->n_rows * s->Cp);
-    }
-    if (flt) {
-      rows.add(&d_flt_src, flt->rows, (size_t)flt->n_rows * Wc);
-      rows.add(&d_flt_rows, (size_t)flt->n_rows * s->W);
-    }
-    HIPCHK(rows.alloc());
-    HIPCHK(rows.upload(e->stream));
     // (KP_PACK_TIMING: the two kernels' times between the engine's stage events, idle here)
+    const dev::event_t tev[3] = {e->ev[EV_ROWS_BEGIN], e->ev[EV_ROWS_END], e->ev[EV_SELECT_BEGIN]};
     const bool timing = kp_env_flag("KP_PACK_TIMING");
-    if (timing) HIPCHK(dev::event_record(e->ev[EV_ROWS_BEGIN], e->stream));
-    if (est) HIPCHK(dev::est_rows_rank(e->stream, s->view, d_est_src, (int)est->n_rows, d_est_rows));
-    if (timing) HIPCHK(dev::event_record(e->ev[EV_ROWS_END], e->stream));
-    if (flt) HIPCHK(dev::flt_rows_rank(e->stream, s->view, d_flt_src, (int)flt->n_rows, d_flt_rows));
-    if (timing) HIPCHK(dev::event_record(e->ev[EV_SELECT_BEGIN], e->stream));
+    Arena staging;
+    if (int rc = make_answer_rows(e, s, est, flt, e->stream, &staging, timing ? tev : nullptr, &rows)) {
+      (void)dev::sync(e->stream);  // (what was queued uses the blocks that go back to the pool)
+      return rc;
+    }
     HIPCHK(dev::sync(e->stream));  // (the caller's rows are read; the batches' streams may start)
     if (timing)
       fprintf(stderr, "kp_schedule_affinities_ex: k_est_rows_rank %u rows %.1f us, k_flt_rows_rank %u rows %.1f us, %zu bytes uploaded\n",
-              est ? est->n_rows : 0, 1e3 * dev::event_ms(e->ev[EV_ROWS_BEGIN], e->ev[EV_ROWS_END]),
-              flt ? flt->n_rows : 0, 1e3 * dev::event_ms(e->ev[EV_ROWS_END], e->ev[EV_SELECT_BEGIN]),
-              (est ? 4 * (size_t)est->n_rows * s->C : 0) + (flt ? 8 * (size_t)flt->n_rows * Wc : 0));
+              rows->n_est, 1e3 * dev::event_ms(tev[0], tev[1]), rows->n_flt, 1e3 * dev::event_ms(tev[1], tev[2]),
+              4 * (size_t)rows->n_est * s->C + 8 * (size_t)rows->n_flt * (((size_t)s->C + 63) / 64));
   }
   std::vector<int32_t> sub_est;
   auto& A = e->aff;
@@ -1827,28 +1785,22 @@ int kp_schedule_affinities_ex(kp_engine* e, const kp_snapshot* s, const kp_bindi
         sub[j].observed_affinity_name = sub[j].cluster_affinities[cur[pending[j]]].affinity_name;
     }
     kp_batch* bt = nullptr;
-    int rc;
-    if (lend) {  // this round's row_of and (binding, row) pairs from the pending list and each current term
-      LentRows lent;
-      lent.flt_plugins = flt_plugins;
-      if (est) {
-        sub_est.resize(pending.size());
-        for (size_t j = 0; j < pending.size(); j++) sub_est[j] = est->row_of[pending[j]];
-        lent.est_row_of = sub_est.data();
-        lent.d_est_rows = d_est_rows;
-      }
-      if (flt) {
-        for (size_t j = 0; j < pending.size(); j++) {
-          const uint64_t i = pending[j];
-          const int32_t r = flt->row_of[term_off[i] + (bs[i].n_cluster_affinities ? cur[i] : 0)];
-          if (r >= 0) lent.flt_list.push_back(FltPair{(int32_t)j, r});
-        }
-        lent.d_flt_rows = d_flt_rows;
-      }
-      rc = batch_create_lent(e, s, sub.data(), sub.size(), &lent, &bt);
-    } else {
-      rc = kp_batch_create(e, s, sub.data(), sub.size(), &bt);
+    // this round's row_of and (binding, row) pairs from the pending list and each current term
+    BatchAnswers a;
+    a.rows = rows;
+    a.flt_plugins = flt_plugins;
+    if (est) {
+      sub_est.resize(pending.size());
+      for (size_t j = 0; j < pending.size(); j++) sub_est[j] = est->row_of[pending[j]];
+      a.est_row_of = sub_est.data();
     }
+    if (flt)
+      for (size_t j = 0; j < pending.size(); j++) {
+        const uint64_t i = pending[j];
+        const int32_t r = flt->row_of[term_off[i] + (bs[i].n_cluster_affinities ? cur[i] : 0)];
+        if (r >= 0) a.flt_list.push_back(FltPair{(int32_t)j, r});
+      }
+    int rc = batch_create_with(e, s, sub.data(), sub.size(), nullptr, nullptr, &a, &bt);
     if (rc) return rc;
     kp_results r{};
     rc = kp_schedule_batch(e, bt, &r);

@@ -308,6 +308,47 @@ int md_cap_of(const kp_snapshot* s);
 int batch_lds_check(kp_engine* e, const kp_snapshot* s, const kp_batch* bt);
 int build_sets_args(const kp_snapshot* s, const kp_component* comps, uint32_t K, SetsArgs* A, std::string* err);
 
+// The one intake (answers.cpp) of kp_estimates and kp_filter_answers for kp_batch_create_estimates
+// / _filters and kp_schedule_affinities_ex. The checks: `who` is the entry point's name, `pre`
+// how it names the input's fields ("", or "est->" / "flt->" in the affinity call), n the call's
+// bindings; an input that is null or without rows passes. check_estimates is every estimate
+// check. check_filters ends with the n_rows bound; the verdicts' row_of range is check_row_of
+// over [first, first + count): n entries, or one binding's between the term_off checks.
+int check_estimates(kp_engine* e, const kp_snapshot* s, const char* who, const char* pre, const kp_estimates* est,
+                    uint64_t n);
+int check_filters(kp_engine* e, const kp_snapshot* s, const char* who, const char* pre, const kp_filter_answers* flt,
+                  uint64_t n);
+int check_row_of(kp_engine* e, const char* who, const char* pre, const int32_t* row_of, uint64_t first, uint64_t count,
+                 uint32_t n_rows);
+// Checked rows on the device in rank order: d_est [n_est][Cp], -1 in [C, Cp); d_flt [n_flt][W],
+// zero bits at and above C. The batches made over them share it (kp_batch::rows); its block
+// goes back to the engine device's buffer pool with the last holder.
+struct AnswerRows {
+  Arena dev;
+  int32_t* d_est = nullptr;
+  uint64_t* d_flt = nullptr;
+  uint32_t n_est = 0, n_flt = 0;
+};
+// *out from checked est / flt (null: none), queued on `st`: the caller's arrays go up in caller
+// order into `staging`, k_est_rows_rank / k_flt_rows_rank rank them. Nothing waits here: the
+// caller synchronises `st` before it lets go of its arrays, of `staging` or, after an error, of
+// *out. tev: three events recorded around the two kernels (KP_PACK_TIMING), or null.
+int make_answer_rows(kp_engine* e, const kp_snapshot* s, const kp_estimates* est, const kp_filter_answers* flt,
+                     dev::stream_t st, Arena* staging, const dev::event_t* tev, std::shared_ptr<const AnswerRows>* out);
+// A batch's part of the answers. A kp_batch_create* call gives est / flt unchecked: creation
+// checks them before it packs, fills the rest, and makes the rows once a class or a binding
+// is known to have one. kp_schedule_affinities_ex gives its `rows` (or null), the bindings'
+// estimate rows (null: none), the (binding, verdict row) pairs in binding order and the number
+// of registered plugins the verdicts fold in.
+struct BatchAnswers {
+  const kp_estimates* est = nullptr;
+  const kp_filter_answers* flt = nullptr;
+  std::shared_ptr<const AnswerRows> rows;
+  const int32_t* est_row_of = nullptr;
+  std::vector<FltPair> flt_list;
+  uint32_t flt_plugins = 0;
+};
+
 }  // namespace kp::host
 using namespace kp::host;
 
@@ -465,10 +506,10 @@ struct kp_batch {
   FltPair* d_flt_list = nullptr;
   uint64_t* d_flt_rows = nullptr;
   uint32_t flt_plugins = 0;
-  // false: d_est_rows / d_flt_rows are lent by a call that made them for several batches
-  // (kp_schedule_affinities_ex, one batch a round): they lie outside this batch's arena, and
-  // the lender frees them after its last batch is destroyed.
-  bool owns_rows = true;
+  // d_est_rows / d_flt_rows point into `rows` (answers.cpp), which this batch shares with
+  // whoever else was created over the same answers (kp_schedule_affinities_ex: one batch a
+  // round) and which goes back to the pool with the last of them; null for a batch without.
+  std::shared_ptr<const AnswerRows> rows;
   // component-set classes (BF_SETS): class id and resolved component list of each;
   // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
   // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)
@@ -580,18 +621,7 @@ struct kp_batch {
   std::vector<RegionOut> h_rout;
 };
 
-// kp_batch_create_filters for a batch that borrows its rows (pack.cpp; kp_schedule_affinities_ex
-// calls it once a round): the rows are on the device already, in rank order with their
-// padding ([..][Cp] of -1, [..][W] of zero bits), checked by the lender. est_row_of: the
-// n bindings' estimate rows (null: none); flt_list: the bindings that have a verdict row, in
-// binding order (taken over). The batch neither copies nor frees the rows.
-struct LentRows {
-  const int32_t* est_row_of = nullptr;
-  int32_t* d_est_rows = nullptr;
-  std::vector<FltPair> flt_list;
-  uint64_t* d_flt_rows = nullptr;
-  uint32_t flt_plugins = 0;
-};
-int batch_create_lent(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n, LentRows* lent,
-                      kp_batch** out);
-
+// The one creation function behind the four kp_batch_create* entry points and every round
+// of kp_schedule_affinities_ex (pack.cpp); keys and cache may be null.
+int batch_create_with(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n,
+                      const kp_binding_key* keys, kp_pack_cache* cache, BatchAnswers* ans, kp_batch** out);

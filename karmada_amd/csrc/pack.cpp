@@ -1370,28 +1370,26 @@ static int64_t order_amort() {  // (read per batch: tests switch it)
   return std::max<int64_t>(0, kp_env_int("KP_ORDER_AMORT", 4));
 }
 
-static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
-                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est = nullptr, const kp_filter_answers* flt = nullptr,
-                             LentRows* lent = nullptr);
 int kp_batch_create_filters(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                             uint64_t n, kp_pack_cache* cache, const kp_estimates* est, const kp_filter_answers* flt,
                             kp_batch** out) {
   if (cache && n && !keys) return KP_EINVAL;  // (as kp_batch_create_keyed)
-  return batch_create_impl(e, sc, bindings, n, cache ? keys : nullptr, cache, out, est, flt);
+  BatchAnswers a;
+  a.est = est;
+  a.flt = flt;
+  return batch_create_with(e, sc, bindings, n, cache ? keys : nullptr, cache, &a, out);
 }
 int kp_batch_create_estimates(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                               uint64_t n, kp_pack_cache* cache, const kp_estimates* est, kp_batch** out) {
-  if (cache && n && !keys) return KP_EINVAL;  // (as kp_batch_create_keyed)
-  return batch_create_impl(e, sc, bindings, n, cache ? keys : nullptr, cache, out, est);
+  return kp_batch_create_filters(e, sc, bindings, keys, n, cache, est, nullptr, out);
 }
 int kp_batch_create(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n, kp_batch** out) {
-  return batch_create_impl(e, sc, bindings, n, nullptr, nullptr, out);
+  return kp_batch_create_filters(e, sc, bindings, nullptr, n, nullptr, nullptr, nullptr, out);
 }
 int kp_batch_create_keyed(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                           uint64_t n, kp_pack_cache* cache, kp_batch** out) {
   if (!cache || (n && !keys)) return KP_EINVAL;
-  return batch_create_impl(e, sc, bindings, n, keys, cache, out);
+  return kp_batch_create_filters(e, sc, bindings, keys, n, cache, nullptr, nullptr, out);
 }
 int kp_batch_digest(const kp_batch* b, uint64_t* out) {
   if (!b || !out) return KP_EINVAL;
@@ -1431,23 +1429,22 @@ int kp_pack_cache_get_stats(const kp_pack_cache* c, kp_pack_cache_stats* out) {
   out->last_hits = c->last_hits;
   return KP_OK;
 }
-// kp_batch_create runs in stages (take_estimates ... upload, in that order); CreateCtx is
+void kp_batch_destroy(kp_batch* b) { delete b; }
+
+}  // extern "C"
+
+// batch_create_with runs in stages (take_answers ... upload, in that order); CreateCtx is
 // what they share. Every host array the arena uploads from and no kp_batch member keeps
-// lives here, so it outlives the upload's sync by construction.
+// lives here, with the rows' staging copy, so it outlives the upload's sync by construction.
 namespace {
 struct CreateCtx {
   kp_engine* e;
   kp_snapshot* s;
   const kp_binding* bindings;
   uint64_t n;
-  const kp_estimates* est;         // null once found empty
-  const kp_filter_answers* flt;    // null once found empty
-  LentRows* lent;                  // rows the batch borrows instead (est and flt null), or null
+  BatchAnswers& ans;               // est / flt null once found empty or unused
   kp_batch* bt = nullptr;
-  std::vector<int32_t> est_rows;   // kp_estimates rows by cluster rank, [n_rows][Cp]
-  std::vector<uint64_t> flt_rows;  // kp_filter_answers rows by cluster rank, [n_rows][W]
-  std::vector<FltPair> flt_list;   // the bindings that have a filter row
-  uint32_t flt_plugins = 0;
+  Arena staging;                   // the caller-order rows make_answer_rows ranks on the device
   std::vector<int32_t> rep;        // d_crep's source: crep, -1 in the component-set classes
   std::vector<int64_t> sets_off;   // per cluster rank, its node-run scratch offset
   bool with_orders = false;
@@ -1455,81 +1452,24 @@ struct CreateCtx {
 };
 }  // namespace
 
-// What the two optional inputs' checks share: the n_clusters check that opens them and the
-// n_rows bound and row_of range that close them; each input's own checks come between.
-static int bad_answers(CreateCtx& c, const char* who, const std::string& why) {
-  c.e->err = std::string(who) + ": " + why;
-  return KP_EINVAL;
-}
-static int check_clusters(CreateCtx& c, const char* who, uint64_t n_clusters) {
-  if (n_clusters == (uint64_t)c.s->C) return KP_OK;
-  return bad_answers(c, who, "n_clusters is " + std::to_string(n_clusters) + ", the snapshot holds " +
-                                 std::to_string(c.s->C) + " clusters");
-}
-static int check_row_of(CreateCtx& c, const char* who, uint32_t n_rows, const int32_t* row_of) {
-  if (n_rows > (uint32_t)INT32_MAX) return bad_answers(c, who, "more than 2^31 - 1 rows");
-  for (uint64_t i = 0; i < c.n; i++)
-    if (row_of[i] < -1 || row_of[i] >= (int64_t)n_rows)
-      return bad_answers(c, who, "row_of[" + std::to_string(i) + "] = " + std::to_string(row_of[i]) +
-                                     " is outside -1.." + std::to_string((int64_t)n_rows - 1));
-  return KP_OK;
-}
-
-// Stage 1a: the other estimators' rows (kp_estimates), checked and brought into rank order
-// with the device rows' padding (-1: no answer) before anything is packed; none: est null.
-static int take_estimates(CreateCtx& c) {
-  const kp_estimates* est = c.est;
-  kp_snapshot* s = c.s;
-  if (est && est->n_rows == 0) est = c.est = nullptr;
-  if (!est) return KP_OK;
-  const char* who = "kp_batch_create_estimates";
-  if (int rc = check_clusters(c, who, est->n_clusters)) return rc;
-  if (!est->rows || (c.n && !est->row_of)) return bad_answers(c, who, "rows or row_of is null");
-  if (int rc = check_row_of(c, who, est->n_rows, est->row_of)) return rc;
-  c.est_rows.assign((size_t)est->n_rows * s->Cp, -1);
-  for (uint32_t r = 0; r < est->n_rows; r++) {
-    const int32_t* src = est->rows + (size_t)r * s->C;
-    int32_t* dst = c.est_rows.data() + (size_t)r * s->Cp;
-    for (int k = 0; k < s->C; k++) {
-      const int32_t v = src[s->perm[k]];
-      if (v < -1)
-        return bad_answers(c, who, "rows[" + std::to_string(r) + "][" + std::to_string(s->perm[k]) + "] = " +
-                                       std::to_string(v) + " is below -1 (UnauthenticReplica)");
-      dst[k] = v;
-    }
-  }
-  return KP_OK;
-}
-
-// Stage 1b: the out-of-tree filter verdicts (kp_filter_answers), checked and brought into
-// rank order (dev_row bit rank = caller_row bit perm[rank]; W words a row, zero bits in the
-// padding, caller bits at or above C never read), and the bindings that have a row.
-static int take_filters(CreateCtx& c) {
-  const kp_filter_answers* flt = c.flt;
-  kp_snapshot* s = c.s;
-  c.flt_plugins = flt ? flt->n_plugins : 0;
-  if (flt && flt->n_rows == 0) flt = c.flt = nullptr;
-  if (!flt) return KP_OK;
+// Stage 1: a kp_batch_create* call's own inputs (BatchAnswers::est / flt) checked before
+// anything is packed, the estimates first, and the batch's part taken from them; an input
+// without rows, or verdicts no binding has a row of, counts as none from here on.
+static int take_answers(CreateCtx& c) {
+  BatchAnswers& a = c.ans;
+  if (int rc = check_estimates(c.e, c.s, "kp_batch_create_estimates", "", a.est, c.n)) return rc;
+  if (a.est && a.est->n_rows == 0) a.est = nullptr;
+  if (a.est) a.est_row_of = a.est->row_of;
+  if (!a.flt) return KP_OK;
   const char* who = "kp_batch_create_filters";
-  if (int rc = check_clusters(c, who, flt->n_clusters)) return rc;
-  if (!flt->rows) return bad_answers(c, who, "rows is null");
-  if (c.n && !flt->row_of) return bad_answers(c, who, "row_of is null");
-  if (flt->n_plugins == 0)
-    return bad_answers(c, who, "n_rows is " + std::to_string(flt->n_rows) + " with n_plugins == 0");
-  if (int rc = check_row_of(c, who, flt->n_rows, flt->row_of)) return rc;
+  a.flt_plugins = a.flt->n_plugins;
+  if (int rc = check_filters(c.e, c.s, who, "", a.flt, c.n)) return rc;
+  if (a.flt->n_rows == 0) a.flt = nullptr;
+  if (!a.flt) return KP_OK;
+  if (int rc = check_row_of(c.e, who, "", a.flt->row_of, 0, c.n, a.flt->n_rows)) return rc;
   for (uint64_t i = 0; i < c.n; i++)
-    if (flt->row_of[i] >= 0) c.flt_list.push_back(FltPair{(int32_t)i, flt->row_of[i]});
-  if (c.flt_list.empty()) return KP_OK;  // (rows that no binding uses: nothing to merge)
-  const size_t Wc = ((size_t)s->C + 63) / 64;
-  c.flt_rows.assign((size_t)flt->n_rows * s->W, 0);
-  for (uint32_t r = 0; r < flt->n_rows; r++) {
-    const uint64_t* src = flt->rows + (size_t)r * Wc;
-    uint64_t* dst = c.flt_rows.data() + (size_t)r * s->W;
-    for (int k = 0; k < s->C; k++) {
-      const uint32_t cl = s->perm[k];
-      dst[k >> 6] |= ((src[cl >> 6] >> (cl & 63)) & 1) << (k & 63);
-    }
-  }
+    if (a.flt->row_of[i] >= 0) a.flt_list.push_back(FltPair{(int32_t)i, a.flt->row_of[i]});
+  if (a.flt_list.empty()) a.flt = nullptr;
   return KP_OK;
 }
 
@@ -1807,18 +1747,10 @@ static int plan_arena(CreateCtx& c) {
   if (!bt->l_est_cls.empty()) {
     a.add(&bt->d_cls_est, bt->cls_est.data(), bt->cls_est.size());
     a.add(&bt->d_est_cls, bt->l_est_cls.data(), bt->l_est_cls.size());
-    if (bt->owns_rows) a.add(&bt->d_est_rows, c.est_rows.data(), c.est_rows.size());
   }
-  if (!bt->l_flt.empty()) {
-    a.add(&bt->d_flt_list, bt->l_flt.data(), bt->l_flt.size());
-    if (bt->owns_rows) a.add(&bt->d_flt_rows, c.flt_rows.data(), c.flt_rows.size());
-  }
+  if (!bt->l_flt.empty()) a.add(&bt->d_flt_list, bt->l_flt.data(), bt->l_flt.size());
   c.tp1 = std::chrono::steady_clock::now();
   HIPCHK(a.alloc());
-  if (!bt->owns_rows) {  // (outside the arena: ~kp_batch leaves them to the lender)
-    bt->d_est_rows = c.lent->d_est_rows;
-    bt->d_flt_rows = c.lent->d_flt_rows;
-  }
   bt->h_kargs = (KArgs*)pinned_get(sizeof(KArgs) * kArgSlots, &bt->h_kargs_bytes);
   if (!bt->h_kargs) {
     e->err = "kp_batch_create: page-locked launch-argument slots";
@@ -1827,25 +1759,35 @@ static int plan_arena(CreateCtx& c) {
   return KP_OK;
 }
 
-// Stage 6: the copies, k_slow's flags cleared, the sync, and the KP_PACK_TIMING lines.
-// create_stream is set while copies may be queued: an early return waits for them in
-// ~kp_batch before the arena goes back to the pool.
+// Stage 6: the copies, the rows of a kp_batch_create* call's own inputs when a class or a
+// binding has one (ranked on the device, unprofiled), k_slow's flags cleared, the sync, and
+// the KP_PACK_TIMING lines. create_stream is set while work may be queued: an early return
+// waits for it in ~kp_batch before the arena and the rows go back to the pool.
 static int upload(CreateCtx& c) {
   kp_engine* e = c.e;
   kp_batch* bt = c.bt;
+  kp_snapshot* s = c.s;
   const int B = bt->B ? bt->B : 1;
   bt->create_stream = e->stream;
   c.tp2 = std::chrono::steady_clock::now();
   HIPCHK(bt->dev.upload(e->stream));
+  const kp_estimates* est = bt->l_est_cls.empty() ? nullptr : c.ans.est;
+  const kp_filter_answers* flt = bt->l_flt.empty() ? nullptr : c.ans.flt;
+  if (est || flt)
+    if (int rc = make_answer_rows(e, s, est, flt, e->stream, &c.staging, nullptr, &bt->rows)) return rc;
+  if (bt->rows) bt->d_est_rows = bt->rows->d_est, bt->d_flt_rows = bt->rows->d_flt;
   HIPCHK(dev::fill(bt->slow, 0, 4 * (size_t)B, e->stream));
   HIPCHK(dev::sync(e->stream));
+  c.staging.reset();
   if (kp_env_flag("KP_PACK_TIMING")) {
     if (!bt->l_est_cls.empty())
       fprintf(stderr, "kp_batch_create_estimates: %zu classes with a row, %zu bytes uploaded for them\n",
-              bt->l_est_cls.size(), 4 * (bt->cls_est.size() + bt->l_est_cls.size() + c.est_rows.size()));
+              bt->l_est_cls.size(),
+              4 * (bt->cls_est.size() + bt->l_est_cls.size() + (est ? (size_t)est->n_rows * s->C : 0)));
     if (!bt->l_flt.empty())
       fprintf(stderr, "kp_batch_create_filters: %zu bindings with a row, %zu bytes uploaded for them\n",
-              bt->l_flt.size(), sizeof(FltPair) * bt->l_flt.size() + 8 * c.flt_rows.size());
+              bt->l_flt.size(),
+              sizeof(FltPair) * bt->l_flt.size() + (flt ? 8 * (size_t)flt->n_rows * (((size_t)s->C + 63) / 64) : 0));
     const auto tp3 = std::chrono::steady_clock::now();
     auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     fprintf(stderr, "kp_batch_create: pack %.1f ms, alloc %.1f ms, upload %.1f ms\n", ms(c.tp0, c.tp1),
@@ -1857,31 +1799,24 @@ static int upload(CreateCtx& c) {
 
 // The validations come in this order, which decides the error a call wrong in two ways
 // sees: estimates, filters, the components check, then the packer.
-static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
-                             const kp_binding_key* keys, kp_pack_cache* cache, kp_batch** out,
-                             const kp_estimates* est, const kp_filter_answers* flt, LentRows* lent) {
+int batch_create_with(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n,
+                      const kp_binding_key* keys, kp_pack_cache* cache, BatchAnswers* ans, kp_batch** out) {
   if (!e || !sc || !out || (n && !bindings)) return KP_EINVAL;
   if (n > (uint64_t)INT32_MAX) return KP_ENOTSUP;
   (void)dev::set_device(e->device);
-  CreateCtx c{e, const_cast<kp_snapshot*>(sc), bindings, n, est, flt, lent};
+  CreateCtx c{e, const_cast<kp_snapshot*>(sc), bindings, n, *ans};
   kp_snapshot* s = c.s;
-  if (int rc = take_estimates(c)) return rc;
-  if (int rc = take_filters(c)) return rc;
+  if (int rc = take_answers(c)) return rc;
   auto* bt = new kp_batch();
   std::unique_ptr<kp_batch> guard(bt);
   c.bt = bt;
   bt->snap = s;
   bt->B = (int)n;
   bt->hdr.resize(n);
-  bt->flt_plugins = c.flt_plugins;
-  bt->l_flt = std::move(c.flt_list);
-  const int32_t* est_row_of = c.est ? c.est->row_of : nullptr;
-  if (lent) {
-    bt->owns_rows = false;
-    bt->flt_plugins = lent->flt_plugins;
-    bt->l_flt = std::move(lent->flt_list);
-    est_row_of = lent->est_row_of;
-  }
+  bt->rows = ans->rows;
+  bt->flt_plugins = ans->flt_plugins;
+  bt->l_flt = std::move(ans->flt_list);
+  const int32_t* est_row_of = ans->est_row_of;
   c.tp0 = std::chrono::steady_clock::now();
   if (s->opts.multiple_pod_templates_scheduling)
     for (uint64_t i = 0; i < n; i++)
@@ -1901,13 +1836,4 @@ static int batch_create_impl(kp_engine* e, const kp_snapshot* sc, const kp_bindi
   if (int rc = upload(c)) return rc;
   *out = guard.release();
   return KP_OK;
-}
-
-void kp_batch_destroy(kp_batch* b) { delete b; }
-
-}  // extern "C"
-
-int batch_create_lent(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, uint64_t n, LentRows* lent,
-                      kp_batch** out) {
-  return batch_create_impl(e, sc, bindings, n, nullptr, nullptr, out, nullptr, nullptr, lent);
 }

@@ -10,7 +10,8 @@
 // synthetic universes lack (several affinity terms, a list of more than 64 values,
 // more than four tolerations, spec.Clusters members with eviction tasks) through
 // the bitset filter, every (binding, cluster) pair against the oracle's filter.
-// run_affinity_answers runs kp_schedule_affinities_ex with both answers (borrowed rows).
+// run_affinity_answers runs kp_schedule_affinities_ex with both answers (rows shared by the
+// rounds' batches), run_batch_answers one batch created with both and scheduled twice.
 // Exit code 0 = no mismatch (the sanitizers abort on their own findings).
 #include <algorithm>
 #include <cstdio>
@@ -363,10 +364,10 @@ static int run_filter_shapes(kp_engine* e) {
 }
 
 // kp_schedule_affinities_ex with both answers over a universe with multi-term bindings: the
-// rows go up once and every round's batch borrows them, so the sanitizer sees them freed
+// rows go up once and every round's batch shares them, so the sanitizer sees them freed
 // exactly once (a second free or a leak aborts the run). Three calls: rows that change
 // nothing (the oracle's retry driver is the reference); rows that reject everything on each
-// binding's first term and halve the estimates, so that later rounds run on borrowed rows;
+// binding's first term and halve the estimates, so that later rounds run on the shared rows;
 // and a call whose first round's batch creation fails (a binding with n_components > 0 and
 // no components under the MultiplePodTemplatesScheduling gate) after the rows were made.
 static int run_affinity_answers(kp_engine* e) {
@@ -458,6 +459,63 @@ static int run_affinity_answers(kp_engine* e) {
   return bad ? 1 : 0;
 }
 
+// One batch created with both inputs (kp_batch_create_filters), scheduled twice and destroyed:
+// the caller's rows go up in caller order, are ranked on the device into rows the batch
+// holds, and the staging copy is let go inside the creation. The rows change nothing
+// (MaxInt32 / -1 estimates, all-ones verdicts with stray bits above C), so both calls give
+// the oracle's placements; the sanitizer sees the rows' block freed once, with the batch.
+static int run_batch_answers(kp_engine* e) {
+  kps_world* w = nullptr;
+  const uint32_t C = 150;
+  if (kps_create(6, 6, C, 0, 300, &w)) return 1;
+  uint64_t nc = 0, nb = 0;
+  const kp_cluster* cl = kps_clusters(w, &nc);
+  const kp_binding* bs = kps_bindings(w, &nb);
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  kpo_world* ow = kpo_world_create(cl, nc, &o);
+  kpo_results* want = nullptr;
+  kpo_schedule(ow, bs, nb, KPO_FAST, 4, &want);
+  o.n_out_of_tree_plugins = 1;
+  const uint64_t wc = (nc + 63) / 64;
+  std::vector<int32_t> erows(2 * nc, INT32_MAX), erow_of(nb), frow_of(nb);
+  std::fill(erows.begin() + (long)nc, erows.end(), -1);
+  std::vector<uint64_t> frows(2 * wc, ~0ull);
+  for (uint64_t i = 0; i < nb; i++) erow_of[i] = (int32_t)(i % 3) - 1, frow_of[i] = (int32_t)((i + 1) % 3) - 1;
+  const kp_estimates est{2, nc, erows.data(), erow_of.data()};
+  const kp_filter_answers flt{2, nc, frows.data(), frow_of.data(), 1};
+  kp_snapshot* s = nullptr;
+  kp_batch* b = nullptr;
+  int bad = 0;
+  if (kp_snapshot_create(e, cl, nc, &o, &s) || kp_batch_create_filters(e, s, bs, nullptr, nb, nullptr, &est, &flt, &b)) {
+    fprintf(stderr, "batch answers: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  }
+  for (int call = 0; call < 2 && !bad; call++) {
+    kp_results r{};
+    if (kp_schedule_batch(e, b, &r)) {
+      fprintf(stderr, "batch answers: call %d: engine error: %s\n", call, kp_last_error(e));
+      bad++;
+      break;
+    }
+    for (uint64_t i = 0; i < nb; i++) {
+      const bool same = r.status[i] == want->status[i] && r.err_code[i] == want->err_code[i] &&
+                        r.err_arg[i] == want->err_arg[i] &&
+                        targets_of(r.offsets, r.cluster_idx, r.replicas, i) ==
+                            targets_of(want->offsets, want->cluster_idx, want->replicas, i);
+      if (!same && bad++ < 3) fprintf(stderr, "batch answers: call %d binding %llu differs\n", call, (unsigned long long)i);
+    }
+  }
+  if (b) kp_batch_destroy(b);
+  if (s) kp_snapshot_destroy(s);
+  kpo_results_free(want);
+  kpo_world_destroy(ow);
+  kps_destroy(w);
+  printf("batch answers: %llu bindings x %u clusters, two calls, %d mismatches\n", (unsigned long long)nb, C, bad);
+  return bad ? 1 : 0;
+}
+
 // `driver ceiling`: the snapshots at which a workgroup's LDS is full (tests/test_lds_ceiling.py:
 // 18 624 clusters without spread bindings, 14 336 with them, and the class-order switch at
 // 16 384 / 16 385) instead of the small universes, so the sanitizer sees every global array
@@ -478,6 +536,7 @@ int main(int argc, char** argv) {
   for (auto& c : cases) fails += run_case(e, std::get<0>(c), std::get<1>(c), std::get<2>(c), std::get<3>(c), std::get<4>(c));
   if (!ceiling) fails += run_filter_shapes(e);
   if (!ceiling) fails += run_affinity_answers(e);
+  if (!ceiling) fails += run_batch_answers(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
