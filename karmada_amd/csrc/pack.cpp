@@ -2,6 +2,13 @@
 // and filters forms, kp_batch_digest, kp_batch_destroy and kp_pack_cache_*. The Packer, the
 // worker threads it runs on, the per-binding routes, the cached records, and the stages of
 // kp_batch_create. Defines valid_req (kp_host.h).
+//
+// pack_parallel packs a batch in stages that share a PackCtx: prepare_cache, pack_chunks,
+// unify_classes, merge_chunks, fill_cache, pick_representatives, and report_timing under
+// KP_PACK_TIMING. Within pack_chunks a ChunkPacker (one per thread) takes each binding through
+// look_ahead, then take_hit or pack_fresh, class_key and, for a keyed miss, make_record.
+// shift_binding is the one routine that knows which fields are offsets into which pool;
+// records and the chunk merge both rebase through it.
 #include "kp_host.h"
 #include "kp_pdq.h"
 #include "kp_top.h"
@@ -10,7 +17,7 @@
 // Binding packing
 // ============================================================================
 namespace {
-// Host-side pools of packed bindings (kp_batch's, or one packing thread's).
+// Host-side pools of packed bindings (one packing chunk's; kp_batch has the same five).
 // (aligned to two cache lines: the packing threads fill adjacent chunks' pools at once, and
 // every push_back writes its vector's end pointer; packed 120-B structs shared lines, and
 // 16 threads packed at about a third of the single-thread rate per binding)
@@ -763,17 +770,6 @@ bool batch_fast_ok(const kp_batch* bt) {
   return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-// Packs bindings [0, n) into bt->hdr and bt's pools on T host threads: thread t
-// packs a contiguous chunk into its own Pools (the Packer only reads the snapshot's
-// dictionaries), then the chunks are concatenated and every pool reference is
-// rebased: header offsets, program ids in the ipool lists, Prog::ins_off and the
-// list offsets inside Instr. The result equals a sequential pack (test_abi).
-// Threads: KP_PACK_THREADS, else the CPUs this process may use (hardware threads,
-// capped by a cgroup CPU quota), one per 4096 bindings at most.
 // Estimator class key of a packed binding: everything the GeneralEstimator reads
 // from it (est_load / est_compute_bf / template_md, kp_algo.h): whether it has
 // ReplicaRequirements and its summary and model requests (resource id, divisor).
@@ -872,13 +868,16 @@ inline void pf_strings(const kp_binding& b) {
     }
 }
 
-// Shifts a packed binding's pool references by (di, dl, dt, dp, dn) (ipool, lpool, tols,
-// progs, instrs): its header, the program ids in its ipool lists, its programs'
-// instruction offsets and its instructions' list offsets. ip: the binding's ipool slice
-// (index = header offset - h.ip_beg, taken before the shift); pr / in: its program and
-// instruction slices. pack_parallel's chunk merge applies the same shifts.
-static void shift_binding(BindHdr& h, int32_t* ip, Prog* pr, int n_pr, Instr* in, int n_in, int32_t di, int32_t dl,
-                          int32_t dt, int32_t dp, int32_t dn) {
+// The pool-reference map, the one copy of it beside Packer::pack, which writes the
+// references: shifts a packed binding's references by (di, dl, dt, dp, dn) (ipool, lpool,
+// tols, progs, instrs). Its header, the program ids in its ipool lists, its programs'
+// instruction offsets and its instructions' list offsets. ip, pr and in point at the
+// binding's own slices [ip_beg, ip_end), [pr_beg, pr_end) and [in_beg, in_end), wherever they
+// lie (a chunk's pools, a record), located before the shift. A cached record's hit, a new
+// record and the chunk merge all rebase through here.
+inline void shift_binding(BindHdr& h, int32_t* ip, Prog* pr, Instr* in, int32_t di, int32_t dl, int32_t dt,
+                          int32_t dp, int32_t dn) {
+  const int n_pr = h.pr_end - h.pr_beg, n_in = h.in_end - h.in_beg;
   for (int j = 0; j < h.filt_cnt; j++) ip[h.filt_off - h.ip_beg + j] += dp;
   for (int j = 0; j < h.ovf_cnt; j++) ip[h.ovf_off - h.ip_beg + j] += dp;
   for (int j = 0; j < h.sw_cnt; j++) ip[h.sw_off - h.ip_beg + j] += dp;
@@ -891,10 +890,8 @@ static void shift_binding(BindHdr& h, int32_t* ip, Prog* pr, int n_pr, Instr* in
   for (int j = 0; j < n_pr; j++) pr[j].ins_off += dn;
   for (int j = 0; j < n_in; j++) {
     Instr& x = in[j];
-    if (x.op == OP_EXCLUDE || x.op == OP_NAMES) x.a += di;
-    else if (x.op == OP_LBL_IN || x.op == OP_LBL_NOTIN || x.op == OP_FLD_IN || x.op == OP_FLD_NOTIN ||
-             x.op == OP_ZONE_IN || x.op == OP_ZONE_NOTIN)
-      x.b += di;
+    if (Packer::list_ref_a(x.op)) x.a += di;
+    else if (Packer::list_ref_b(x.op)) x.b += di;
   }
 }
 
@@ -984,7 +981,7 @@ struct PackTable {
   }
   ~PackTable() { clear(); }
 };
-}  // extern "C"
+}  // namespace
 
 struct kp_pack_cache {
   uint64_t epoch = 0;  // the snapshot epoch the records resolved against (0: none yet)
@@ -1001,8 +998,8 @@ struct kp_pack_cache {
   }
 };
 
-extern "C" {
-static inline uint64_t cache_key(const kp_binding_key& k) {
+namespace {
+inline uint64_t cache_key(const kp_binding_key& k) {
   uint64_t h = 1469598103934665603ull;  // FNV-1a over the uid bytes, then the generation
   for (uint32_t i = 0; i < k.uid.len; i++) h = (h ^ (uint8_t)k.uid.ptr[i]) * 1099511628211ull;
   h ^= (uint64_t)k.generation * 0x9e3779b97f4a7c15ull;
@@ -1010,365 +1007,469 @@ static inline uint64_t cache_key(const kp_binding_key& k) {
   return h ? h : 1;
 }
 
-// row_of (kp_estimates, or null): each binding's row of the other estimators' answers; a
-// workload binding's estimator class is then (request key, row), the row appended to the
-// class key after the record lookup, so a cached record keeps the request key alone.
-bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* bt, const kp_binding_key* keys = nullptr,
-                   kp_pack_cache* cache = nullptr, const int32_t* row_of = nullptr) {
-  int T = (int)kp_env_int("KP_PACK_THREADS", host_cpus());
-  T = std::max(1, std::min(T, n / 4096));
-  // Chunks of kPackChunk bindings taken from a shared counter (a thread that meets heavy
-  // bindings takes fewer chunks); each chunk packs into its own pools, concatenated in
-  // chunk order below. Packer caches and class-id maps are per thread.
-  constexpr int kPackChunk = 1024;
-  const int K = std::max(1, (n + kPackChunk - 1) / kPackChunk);
-  std::vector<Pools> pl(K);
-  std::vector<int> lo(K + 1), owner(K, 0);
-  for (int k = 0; k <= K; k++) lo[k] = std::min(n, k * kPackChunk);
-  // estimator classes: thread-local ids (bt->bcls) and keys, unified below
-  bt->bcls.resize(n);
-  std::vector<std::vector<std::string>> tkeys(T);
-  std::vector<std::string> terr(T);
-  std::vector<double> tms(T, 0.0), tstart(T, 0.0);
-  const auto tpack0 = std::chrono::steady_clock::now();
-  std::atomic<int> next_chunk(0);
-  bt->route.resize(n);
-  std::vector<uint64_t> chunk_cap(K + 1, 0);  // result slots per chunk (out_off prefix sums)
-  std::vector<int> tmax_tgt(T, 0), tmax_tiers(T, 1);
-  // kp_pack_cache: records of another snapshot epoch, or past the size cap, are dropped
-  // first; new records collect per (chunk, shard) and go into the shards after the pack
-  if (cache && (cache->epoch != s->epoch || cache->entries() > cache->max_entries)) {
-    cache->clear();
-    cache->epoch = s->epoch;
+// pack_parallel packs bindings [0, n) into bt->hdr and bt's pools on T host threads. Chunks of
+// kPackChunk bindings are taken from a shared counter (a thread that meets heavy bindings
+// takes fewer chunks); each chunk packs into its own Pools (the Packer only reads the
+// snapshot's dictionaries), then the chunks are concatenated in chunk order and every pool
+// reference is rebased (shift_binding). The result equals a sequential pack (test_abi).
+// Threads: KP_PACK_THREADS, else the CPUs this process may use (hardware threads, capped by a
+// cgroup CPU quota), one per 4096 bindings at most. Packer caches and class-id maps are per
+// thread. PackCtx is what the stages share.
+constexpr int kPackChunk = 1024;
+using PackClock = std::chrono::steady_clock;
+
+struct PackCtx {
+  kp_snapshot* s;
+  const kp_binding* bindings;
+  const int n;
+  kp_batch* bt;
+  const kp_binding_key* keys;
+  kp_pack_cache* cache;
+  // (kp_estimates, or null) each binding's row of the other estimators' answers; a workload
+  // binding's estimator class is then (request key, row), the row appended to the class key
+  // after the record lookup, so a cached record keeps the request key alone
+  const int32_t* row_of;
+  const int T, K;
+  std::vector<int> lo, owner;       // chunk k: bindings [lo[k], lo[k + 1]), and the thread that packed it
+  std::vector<Pools> pl;            // per chunk: its own pools,
+  std::vector<size_t> bi, bl, bo, bp, bn;  // where each of the five goes in the batch's (merge_chunks),
+  std::vector<uint64_t> chunk_cap;  // and its result slots at [k + 1], prefix-summed for out_off
+  // per thread: the estimator class keys by thread-local id (bt->bcls holds those until the
+  // merge) and their global ids, the first error, the headers' maxima and the cache hits
+  // (each written once per chunk: adjacent slots share a line)
+  std::vector<std::vector<std::string>> tkeys;
+  std::vector<std::vector<int32_t>> remaps;
+  std::vector<std::string> terr;
+  std::vector<int> tmax_tgt, tmax_tiers;
+  std::vector<uint64_t> thits;
+  // kp_pack_cache: the new records per (chunk, shard), put into the shards after the merge
+  std::vector<std::vector<PackRec*>> newrecs;
+  // KP_PACK_TIMING: each thread's packing time and start; the pack stage's begin and end
+  std::vector<double> tms, tstart;
+  PackClock::time_point tpack0 = PackClock::now(), tq0, tq1;
+
+  PackCtx(kp_snapshot* s_, const kp_binding* bindings_, int n_, kp_batch* bt_, const kp_binding_key* keys_,
+          kp_pack_cache* cache_, const int32_t* row_of_, int T_)
+      : s(s_), bindings(bindings_), n(n_), bt(bt_), keys(keys_), cache(cache_), row_of(row_of_), T(T_),
+        K(std::max(1, (n_ + kPackChunk - 1) / kPackChunk)), lo(K + 1), owner(K, 0), pl(K), bi(K + 1, 0),
+        bl(K + 1, 0), bo(K + 1, 0), bp(K + 1, 0), bn(K + 1, 0), chunk_cap(K + 1, 0), tkeys(T), remaps(T), terr(T), tmax_tgt(T, 0), tmax_tiers(T, 1), thits(T, 0),
+        tms(T, 0.0), tstart(T, 0.0) {
+    for (int k = 0; k <= K; k++) lo[k] = std::min(n, k * kPackChunk);
   }
-  std::vector<std::vector<PackRec*>> newrecs(cache ? (size_t)K * kCacheShards : 0);
-  struct RecGuard {  // records not handed to the cache (a failed batch) are freed
-    std::vector<std::vector<PackRec*>>* v;
-    ~RecGuard() {
-      for (auto& x : *v)
-        for (PackRec* r : x)
-          if (r) PackRec::free(r);
+  ~PackCtx() {  // records not handed to the cache (a failed batch) are freed
+    for (auto& x : newrecs)
+      for (PackRec* r : x)
+        if (r) PackRec::free(r);
+  }
+  template <class F>
+  void on_threads(F fn) {
+    HostPool::get().run(T, std::function<void(int)>(fn));
+  }
+};
+
+// Stage 1: records of another snapshot epoch, or past the size cap, are dropped before any
+// lookup.
+void prepare_cache(PackCtx& c) {
+  kp_pack_cache* cache = c.cache;
+  if (!cache) return;
+  if (cache->epoch != c.s->epoch || cache->entries() > cache->max_entries) {
+    cache->clear();
+    cache->epoch = c.s->epoch;
+  }
+  c.newrecs.resize((size_t)c.K * kCacheShards);
+}
+
+// Stage 2's worker, one per packing thread: its Packer, its estimator-class ids, and the
+// chunk it is packing. A binding goes through look_ahead, then take_hit or pack_fresh, then
+// class_key, make_record for a keyed miss, and local_class.
+struct ChunkPacker {
+  static constexpr int kRing = 16;
+  PackCtx& c;
+  const int t;
+  Packer pk;
+  SvMap<int32_t> ids;  // class key -> thread-local class id
+  std::string key;     // the class key of the binding in hand
+  SetsArgs A;
+  int hi = 0;          // the chunk's end, its pools, and the lookups in flight
+  Pools* P = nullptr;
+  size_t ip0 = 0, lp0 = 0, to0 = 0, pr0 = 0, in0 = 0;  // where the binding in hand starts in them
+  uint64_t ck_ring[kRing];
+  const PackRec* rec_ring[kRing];
+
+  ChunkPacker(PackCtx& c_, int t_) : c(c_), t(t_), pk{c_.s, nullptr} {}
+
+  // kp_pack_cache lookups run ahead of the packing in stages, each prefetching what the
+  // next one reads: the uid bytes (8 ahead), the key hash and its table slot (4 ahead), the
+  // record (2 ahead); bindings without a record get the packer's own prefetches instead
+  bool keyed_at(int j) const { return c.cache && j < hi && c.keys[j].uid.len > 0; }
+  void stage_hash(int j) {
+    if (!keyed_at(j)) return;
+    const uint64_t ck = cache_key(c.keys[j]);
+    ck_ring[j % kRing] = ck;
+    pf(c.cache->shard[ck % kCacheShards].home_slot(ck));
+  }
+  void stage_rec(int j) {
+    const PackRec* r = nullptr;
+    if (keyed_at(j)) {
+      const uint64_t ck = ck_ring[j % kRing];
+      r = c.cache->shard[ck % kCacheShards].find(ck);
+      if (r)
+        for (int o = 0; o < 8; o++) pf((const char*)r + 64 * o);
     }
-  } rec_guard{&newrecs};
-  std::vector<uint64_t> thits(T, 0);  // (added once per chunk: adjacent slots share a line)
-  auto run = [&](int t) {
-    const auto tt0 = std::chrono::steady_clock::now();
-    struct Stamp {
-      std::chrono::steady_clock::time_point t0;
+    rec_ring[j % kRing] = r;
+    if (!r && j < hi) pf_arrays(c.bindings[j]);
+  }
+  void look_ahead_open(int lo) {  // what look_ahead would have done before the chunk's first binding
+    for (int q = lo; q < std::min(hi, lo + 3); q++) pf_struct(&c.bindings[q]);
+    if (c.cache) {
+      for (int q = lo; q < std::min(hi, lo + 8); q++)
+        if (keyed_at(q)) pf(c.keys[q].uid.ptr);
+      for (int q = lo; q < lo + 4; q++) stage_hash(q);
+      for (int q = lo; q < lo + 2; q++) stage_rec(q);
+    } else if (lo + 1 < hi) {
+      pf_arrays(c.bindings[lo + 1]);
+    }
+  }
+  void look_ahead(int i) {
+    const kp_binding* bindings = c.bindings;
+    if (i + 3 < hi) pf_struct(&bindings[i + 3]);
+    if (c.cache) {
+      if (keyed_at(i + 8)) pf(c.keys[i + 8].uid.ptr);
+      stage_hash(i + 4);
+      stage_rec(i + 2);
+      if (i + 1 < hi && !rec_ring[(i + 1) % kRing]) pf_strings(bindings[i + 1]);
+    } else {
+      if (i + 2 < hi) pf_arrays(bindings[i + 2]);
+      if (i + 1 < hi) pf_strings(bindings[i + 1]);
+    }
+  }
+
+  // A cached record (kp_pack_cache): its slices appended at the pools' ends, and its
+  // references shifted onto them.
+  void take_hit(const PackRec& hit, BindHdr& h) {
+    h = hit.h;
+    P->ipool.insert(P->ipool.end(), hit.ip(), hit.ip() + hit.n_ip);
+    P->lpool.insert(P->lpool.end(), hit.lp(), hit.lp() + hit.n_lp);
+    P->tols.insert(P->tols.end(), hit.tol(), hit.tol() + hit.n_tol);
+    P->progs.insert(P->progs.end(), hit.pr(), hit.pr() + hit.n_pr);
+    P->instrs.insert(P->instrs.end(), hit.in(), hit.in() + hit.n_in);
+    shift_binding(h, P->ipool.data() + ip0, P->progs.data() + pr0, P->instrs.data() + in0, (int32_t)ip0,
+                  (int32_t)lp0, (int32_t)to0, (int32_t)pr0, (int32_t)in0);
+  }
+  void pack_fresh(int i) { pk.pack(c.bindings[i], c.bt->hdr[i]); }
+
+  // The binding's estimator class key into `key`; false for one that calls no estimator
+  // (bcls -1: its row of the other estimators' answers, if any, is ignored).
+  bool class_key(int i, const PackRec* hit) {
+    BindHdr& h = c.bt->hdr[i];
+    if (hit) {
+      if (!hit->nonworkload) key.assign(hit->cls(), hit->cls_len);
+      return !hit->nonworkload;
+    }
+    if (h.flags & BF_NONWORKLOAD_EST) return false;
+    if (h.flags & BF_SETS) {
+      // a component-set class: key 'S' + the resolved SetsArgs (est_key's keys
+      // start with the 0/1 ReplicaRequirements word, never 'S')
+      std::string err;
+      const int rc = build_sets_args(c.s, c.bindings[i].components, c.bindings[i].n_components, &A, &err);
+      if (rc == KP_EINVAL) {
+        h.flags = (h.flags & ~(uint32_t)BF_SETS) | BF_BAD;  // status ERROR, as a bad request
+      } else if (rc != KP_OK) {
+        if (c.terr[t].empty()) c.terr[t] = err;
+        h.flags &= ~(uint32_t)BF_SETS;
+      }
+      c.bt->route[i] = route_of(c.s->view, h, P->lpool.data());  // (flags changed)
+    }
+    if (h.flags & BF_SETS) {
+      key.assign(1, 'S');
+      key.append((const char*)&A, sizeof(A));
+    } else {
+      est_key(h, *P, &key);
+    }
+    return true;
+  }
+
+  // A new record of a keyed binding packed fresh: what the pools hold since the binding's
+  // start, the header with its references relative to those slices, and the fields
+  // PackRec::same compares.
+  void make_record(int i, uint64_t ck, bool workload, std::vector<PackRec*>* shards) {
+    const kp_binding& bb = c.bindings[i];
+    const kp_binding_key& bk = c.keys[i];
+    const uint32_t ul = bk.uid.len, al = bb.observed_affinity_name.len, cl = workload ? (uint32_t)key.size() : 0u;
+    PackRec* r = PackRec::make((int)(P->ipool.size() - ip0), (int)(P->lpool.size() - lp0), (int)(P->tols.size() - to0),
+                               (int)(P->progs.size() - pr0), (int)(P->instrs.size() - in0), (size_t)ul + al + cl);
+    r->key = ck;
+    r->gen = bk.generation;
+    r->has_rt = bb.has_reschedule_triggered_at;
+    r->has_lst = bb.has_last_scheduled_time;
+    r->rt_ns = r->has_rt ? bb.reschedule_triggered_at_ns : 0;
+    r->lst_ns = r->has_lst ? bb.last_scheduled_time_ns : 0;
+    r->nonworkload = workload ? 0 : 1;
+    r->uid_len = ul, r->aff_len = al, r->cls_len = cl;
+    r->h = c.bt->hdr[i];
+    std::copy(P->ipool.begin() + (long)ip0, P->ipool.end(), r->ip());
+    std::copy(P->lpool.begin() + (long)lp0, P->lpool.end(), r->lp());
+    std::copy(P->tols.begin() + (long)to0, P->tols.end(), r->tol());
+    std::copy(P->progs.begin() + (long)pr0, P->progs.end(), r->pr());
+    std::copy(P->instrs.begin() + (long)in0, P->instrs.end(), r->in());
+    if (ul) memcpy((char*)r->uid(), bk.uid.ptr, ul);
+    if (al) memcpy((char*)r->aff(), bb.observed_affinity_name.ptr, al);
+    if (cl) memcpy((char*)r->cls(), key.data(), cl);
+    shift_binding(r->h, r->ip(), r->pr(), r->in(), -(int32_t)ip0, -(int32_t)lp0, -(int32_t)to0, -(int32_t)pr0,
+                  -(int32_t)in0);
+    shards[ck % kCacheShards].push_back(r);
+  }
+
+  // The thread-local id of the class `key` names (with the binding's row, if rows there are).
+  int32_t local_class(int i) {
+    if (c.row_of) key.append((const char*)&c.row_of[i], 4);
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      it = ids.emplace(key, (int32_t)c.tkeys[t].size()).first;
+      c.tkeys[t].push_back(key);
+    }
+    return it->second;
+  }
+
+  void pack_chunk(int k) {
+    kp_batch* bt = c.bt;
+    const int lo = c.lo[k];
+    hi = c.lo[k + 1];
+    P = pk.bt = &c.pl[k];
+    c.owner[k] = t;
+    std::vector<PackRec*>* shards = c.cache ? &c.newrecs[(size_t)k * kCacheShards] : nullptr;
+    uint64_t cap = 0, hits = 0;      // (chunk and thread totals kept in registers: the shared
+    int max_tgt = 0, max_tiers = 1;  // arrays are written once per chunk, not once per binding)
+    look_ahead_open(lo);
+    for (int i = lo; i < hi; i++) {
+      look_ahead(i);
+      // a cached record counts with the same key, generation and status fields
+      const bool keyed = keyed_at(i);
+      const uint64_t ck = keyed ? ck_ring[i % kRing] : 0;
+      const PackRec* hit = keyed ? rec_ring[i % kRing] : nullptr;
+      if (hit && !hit->same(c.keys[i], c.bindings[i])) hit = nullptr;
+      BindHdr& h = bt->hdr[i];
+      ip0 = P->ipool.size(), lp0 = P->lpool.size(), to0 = P->tols.size(), pr0 = P->progs.size(),
+      in0 = P->instrs.size();
+      if (hit) take_hit(*hit, h), hits++;
+      else pack_fresh(i);
+      cap += h.out_cap;
+      bt->route[i] = route_of(c.s->view, h, P->lpool.data());  // (chunk-relative pool offsets)
+      max_tgt = std::max(max_tgt, (int)h.tgt_cnt);
+      max_tiers = std::max(max_tiers, (int)h.ovf_cnt + 2);  // primary, each overflow term, unmatched
+      const bool workload = class_key(i, hit);
+      if (keyed && !hit) make_record(i, ck, workload, shards);
+      bt->bcls[i] = workload ? local_class(i) : -1;
+    }
+    c.chunk_cap[k + 1] = cap;
+    c.thits[t] += hits;
+    c.tmax_tgt[t] = std::max(c.tmax_tgt[t], max_tgt);
+    c.tmax_tiers[t] = std::max(c.tmax_tiers[t], max_tiers);
+  }
+};
+
+// Stage 2: every chunk packed into its own pools, with the headers, the routes and the
+// thread-local classes in the batch's arrays. False, with bt->err, when a thread met an error.
+bool pack_chunks(PackCtx& c) {
+  c.bt->bcls.resize(c.n);
+  c.bt->route.resize(c.n);
+  std::atomic<int> next_chunk(0);
+  c.tq0 = PackClock::now();
+  c.on_threads([&](int t) {
+    struct Stamp {  // (the thread's time, written however it leaves)
+      PackClock::time_point t0;
       double* out;
-      ~Stamp() { *out = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-    } stamp{tt0, &tms[t]};
-    tstart[t] = std::chrono::duration<double, std::milli>(tt0 - tpack0).count();
-    Packer pk{s, nullptr};
-    SvMap<int32_t> ids;
-    std::string key;
-    SetsArgs A;
-    for (;;) {
-      const int k = next_chunk.fetch_add(1);
-      if (k >= K) break;
-      owner[k] = t;
-      pk.bt = &pl[k];
-      uint64_t cap = 0, hits = 0;  // (chunk and thread totals kept in registers: the shared
-      int max_tgt = 0, max_tiers = 1;  // arrays are written once per chunk, not once per binding)
-      const int hi = lo[k + 1];
-      // kp_pack_cache lookups run ahead of the packing in stages, each prefetching what the
-      // next one reads: the uid bytes (8 ahead), the key hash and its table slot (4 ahead), the
-      // record (2 ahead); bindings without a record get the packer's own prefetches instead
-      constexpr int kRing = 16;
-      uint64_t ck_ring[kRing];
-      const PackRec* rec_ring[kRing];
-      auto keyed_at = [&](int j) { return cache && j < hi && keys[j].uid.len > 0; };
-      auto stage_hash = [&](int j) {
-        if (!keyed_at(j)) return;
-        const uint64_t c = cache_key(keys[j]);
-        ck_ring[j % kRing] = c;
-        pf(cache->shard[c % kCacheShards].home_slot(c));
-      };
-      auto stage_rec = [&](int j) {
-        const PackRec* r = nullptr;
-        if (keyed_at(j)) {
-          const uint64_t c = ck_ring[j % kRing];
-          r = cache->shard[c % kCacheShards].find(c);
-          if (r)
-            for (int o = 0; o < 8; o++) pf((const char*)r + 64 * o);
-        }
-        rec_ring[j % kRing] = r;
-        if (!r && j < hi) pf_arrays(bindings[j]);
-      };
-      for (int q = lo[k]; q < std::min(hi, lo[k] + 3); q++) pf_struct(&bindings[q]);
-      if (cache) {
-        for (int q = lo[k]; q < std::min(hi, lo[k] + 8); q++)
-          if (keyed_at(q)) pf(keys[q].uid.ptr);
-        for (int q = lo[k]; q < lo[k] + 4; q++) stage_hash(q);
-        for (int q = lo[k]; q < lo[k] + 2; q++) stage_rec(q);
-      } else if (lo[k] + 1 < hi) {
-        pf_arrays(bindings[lo[k] + 1]);
-      }
-      for (int i = lo[k]; i < hi; i++) {
-        if (i + 3 < hi) pf_struct(&bindings[i + 3]);
-        if (cache) {
-          if (keyed_at(i + 8)) pf(keys[i + 8].uid.ptr);
-          stage_hash(i + 4);
-          stage_rec(i + 2);
-          if (i + 1 < hi && !rec_ring[(i + 1) % kRing]) pf_strings(bindings[i + 1]);
-        } else {
-          if (i + 2 < hi) pf_arrays(bindings[i + 2]);
-          if (i + 1 < hi) pf_strings(bindings[i + 1]);
-        }
-        // a cached record (kp_pack_cache): the same key, generation and status fields
-        const bool keyed = keyed_at(i);
-        const uint64_t ck = keyed ? ck_ring[i % kRing] : 0;
-        const PackRec* hit = keyed ? rec_ring[i % kRing] : nullptr;
-        if (hit && !hit->same(keys[i], bindings[i])) hit = nullptr;
-        Pools& P = pl[k];
-        const size_t ip0 = P.ipool.size(), lp0 = P.lpool.size(), to0 = P.tols.size(), pr0 = P.progs.size(),
-                     in0 = P.instrs.size();
-        if (hit) {  // the record's slices appended, its references shifted onto them
-          BindHdr& h = bt->hdr[i];
-          h = hit->h;
-          P.ipool.insert(P.ipool.end(), hit->ip(), hit->ip() + hit->n_ip);
-          P.lpool.insert(P.lpool.end(), hit->lp(), hit->lp() + hit->n_lp);
-          P.tols.insert(P.tols.end(), hit->tol(), hit->tol() + hit->n_tol);
-          P.progs.insert(P.progs.end(), hit->pr(), hit->pr() + hit->n_pr);
-          P.instrs.insert(P.instrs.end(), hit->in(), hit->in() + hit->n_in);
-          shift_binding(h, P.ipool.data() + ip0, P.progs.data() + pr0, hit->n_pr, P.instrs.data() + in0, hit->n_in,
-                        (int32_t)ip0, (int32_t)lp0, (int32_t)to0, (int32_t)pr0, (int32_t)in0);
-          hits++;
-        } else {
-          pk.pack(bindings[i], bt->hdr[i]);
-        }
-        {
-          const BindHdr& h = bt->hdr[i];
-          cap += h.out_cap;
-          bt->route[i] = route_of(s->view, h, pl[k].lpool.data());  // (chunk-relative pool offsets)
-          max_tgt = std::max(max_tgt, (int)h.tgt_cnt);
-          max_tiers = std::max(max_tiers, (int)h.ovf_cnt + 2);  // primary, each overflow term, unmatched
-        }
-        bool nonworkload = false;
-        if (hit) {
-          nonworkload = hit->nonworkload;
-          if (!nonworkload) key.assign(hit->cls(), hit->cls_len);
-        } else if (bt->hdr[i].flags & BF_NONWORKLOAD_EST) {
-          nonworkload = true;
-        } else {
-          if (bt->hdr[i].flags & BF_SETS) {
-            // a component-set class: key 'S' + the resolved SetsArgs (est_key's keys
-            // start with the 0/1 ReplicaRequirements word, never 'S')
-            std::string err;
-            const int rc = build_sets_args(s, bindings[i].components, bindings[i].n_components, &A, &err);
-            if (rc == KP_EINVAL) {
-              bt->hdr[i].flags = (bt->hdr[i].flags & ~(uint32_t)BF_SETS) | BF_BAD;  // status ERROR, as a bad request
-            } else if (rc != KP_OK) {
-              if (terr[t].empty()) terr[t] = err;
-              bt->hdr[i].flags &= ~(uint32_t)BF_SETS;
-            }
-            bt->route[i] = route_of(s->view, bt->hdr[i], pl[k].lpool.data());  // (flags changed)
-          }
-          if (bt->hdr[i].flags & BF_SETS) {
-            key.assign(1, 'S');
-            key.append((const char*)&A, sizeof(A));
-          } else {
-            est_key(bt->hdr[i], pl[k], &key);
-          }
-        }
-        if (keyed && !hit) {  // a new record: the binding's slices, references relative to them
-          const kp_binding& bb = bindings[i];
-          const uint32_t ul = keys[i].uid.len, al = bb.observed_affinity_name.len,
-                         cl = nonworkload ? 0u : (uint32_t)key.size();
-          PackRec* r = PackRec::make((int)(P.ipool.size() - ip0), (int)(P.lpool.size() - lp0),
-                                     (int)(P.tols.size() - to0), (int)(P.progs.size() - pr0),
-                                     (int)(P.instrs.size() - in0), (size_t)ul + al + cl);
-          r->key = ck;
-          r->gen = keys[i].generation;
-          r->has_rt = bb.has_reschedule_triggered_at;
-          r->has_lst = bb.has_last_scheduled_time;
-          r->rt_ns = r->has_rt ? bb.reschedule_triggered_at_ns : 0;
-          r->lst_ns = r->has_lst ? bb.last_scheduled_time_ns : 0;
-          r->nonworkload = nonworkload ? 1 : 0;
-          r->uid_len = ul, r->aff_len = al, r->cls_len = cl;
-          r->h = bt->hdr[i];
-          std::copy(P.ipool.begin() + (long)ip0, P.ipool.end(), r->ip());
-          std::copy(P.lpool.begin() + (long)lp0, P.lpool.end(), r->lp());
-          std::copy(P.tols.begin() + (long)to0, P.tols.end(), r->tol());
-          std::copy(P.progs.begin() + (long)pr0, P.progs.end(), r->pr());
-          std::copy(P.instrs.begin() + (long)in0, P.instrs.end(), r->in());
-          if (ul) memcpy((char*)r->uid(), keys[i].uid.ptr, ul);
-          if (al) memcpy((char*)r->aff(), bb.observed_affinity_name.ptr, al);
-          if (cl) memcpy((char*)r->cls(), key.data(), cl);
-          shift_binding(r->h, r->ip(), r->pr(), r->n_pr, r->in(), r->n_in, -(int32_t)ip0, -(int32_t)lp0,
-                        -(int32_t)to0, -(int32_t)pr0, -(int32_t)in0);
-          newrecs[(size_t)k * kCacheShards + ck % kCacheShards].push_back(r);
-        }
-        if (nonworkload) {  // (calls no estimator: its row, if any, is ignored)
-          bt->bcls[i] = -1;
-          continue;
-        }
-        if (row_of) key.append((const char*)&row_of[i], 4);
-        auto it = ids.find(key);
-        if (it == ids.end()) {
-          it = ids.emplace(key, (int32_t)tkeys[t].size()).first;
-          tkeys[t].push_back(key);
-        }
-        bt->bcls[i] = it->second;
-      }
-      chunk_cap[k + 1] = cap;
-      thits[t] += hits;
-      tmax_tgt[t] = std::max(tmax_tgt[t], max_tgt);
-      tmax_tiers[t] = std::max(tmax_tiers[t], max_tiers);
-    }
-  };
-  auto on_threads = [&](auto fn) { HostPool::get().run(T, std::function<void(int)>(fn)); };
-  const auto tq0 = std::chrono::steady_clock::now();
-  on_threads(run);
-  const auto tq1 = std::chrono::steady_clock::now();
-  for (auto& x : terr)
+      ~Stamp() { *out = std::chrono::duration<double, std::milli>(PackClock::now() - t0).count(); }
+    } stamp{PackClock::now(), &c.tms[t]};
+    c.tstart[t] = std::chrono::duration<double, std::milli>(stamp.t0 - c.tpack0).count();
+    ChunkPacker w(c, t);
+    for (int k; (k = next_chunk.fetch_add(1)) < c.K;) w.pack_chunk(k);
+  });
+  c.tq1 = PackClock::now();
+  for (auto& x : c.terr)
     if (!x.empty()) {
-      bt->err = x;
+      c.bt->err = x;
       return false;
     }
-  // pools concatenated in chunk order: each chunk's bases are the prefix sums of the
-  // pool sizes before it; the threads rebase the chunks' headers and instructions
-  // and copy their pools into place, chunk by chunk from a shared counter
-  std::vector<size_t> bi(K + 1, 0), bl(K + 1, 0), bo(K + 1, 0), bp(K + 1, 0), bn(K + 1, 0);
-  for (int k = 0; k < K; k++) {
-    bi[k + 1] = bi[k] + pl[k].ipool.size();
-    bl[k + 1] = bl[k] + pl[k].lpool.size();
-    bo[k + 1] = bo[k] + pl[k].tols.size();
-    bp[k + 1] = bp[k] + pl[k].progs.size();
-    bn[k + 1] = bn[k] + pl[k].instrs.size();
-  }
-  if (bi[K] > (size_t)INT32_MAX || bl[K] > (size_t)INT32_MAX || bo[K] > (size_t)INT32_MAX ||
-      bp[K] > (size_t)INT32_MAX || bn[K] > (size_t)INT32_MAX)
-    return false;  // pool offsets are int32
-  bt->ipool.resize(bi[K]);
-  bt->lpool.resize(bl[K]);
-  bt->tols.resize(bo[K]);
-  bt->progs.resize(bp[K]);
-  bt->instrs.resize(bn[K]);
-  // global class ids (1-based; 0 = non-workload): the threads' keys in thread order
+  return true;
+}
+
+// Stage 3: global class ids (1-based; 0 = non-workload) from the threads' keys in thread
+// order, with what a class's key says of it: its row of the other estimators' answers, and
+// the component list of a component-set class.
+void unify_classes(PackCtx& c) {
+  kp_batch* bt = c.bt;
   SvMap<int32_t> gid;
   bt->crep.assign(1, 0);
-  if (row_of) bt->cls_est.assign(1, -1);
-  std::vector<std::vector<int32_t>> remaps(T);
-  for (int t = 0; t < T; t++) {
-    std::vector<int32_t>& remap = remaps[t];
-    remap.resize(tkeys[t].size());
-    for (size_t j = 0; j < tkeys[t].size(); j++) {
-      auto it = gid.emplace(tkeys[t][j], (int32_t)gid.size() + 1).first;
+  if (c.row_of) bt->cls_est.assign(1, -1);
+  for (int t = 0; t < c.T; t++) {
+    std::vector<int32_t>& remap = c.remaps[t];
+    remap.resize(c.tkeys[t].size());
+    for (size_t j = 0; j < c.tkeys[t].size(); j++) {
+      const std::string& key = c.tkeys[t][j];
+      auto it = gid.emplace(key, (int32_t)gid.size() + 1).first;
       remap[j] = it->second;
-      if ((size_t)it->second == bt->crep.size()) {
-        bt->crep.push_back(-1);
-        const std::string& key = tkeys[t][j];
-        if (row_of) {  // the key's last four bytes
-          int32_t r;
-          memcpy(&r, key.data() + key.size() - 4, 4);
-          bt->cls_est.push_back(r);
-          if (r >= 0) bt->l_est_cls.push_back(it->second);
-        }
-        if (!key.empty() && key[0] == 'S') {  // component-set class: its rows come from k_sets_rows
-          SetsArgs A;
-          memcpy(&A, key.data() + 1, sizeof(A));
-          bt->sets_cls.push_back(it->second);
-          bt->sets_args.push_back(A);
-        }
+      if ((size_t)it->second != bt->crep.size()) continue;  // (a class an earlier thread met)
+      bt->crep.push_back(-1);
+      if (c.row_of) {  // the key's last four bytes
+        int32_t r;
+        memcpy(&r, key.data() + key.size() - 4, 4);
+        bt->cls_est.push_back(r);
+        if (r >= 0) bt->l_est_cls.push_back(it->second);
+      }
+      if (!key.empty() && key[0] == 'S') {  // component-set class: its rows come from k_sets_rows
+        SetsArgs A;
+        memcpy(&A, key.data() + 1, sizeof(A));
+        bt->sets_cls.push_back(it->second);
+        bt->sets_args.push_back(A);
       }
     }
   }
-  for (int k = 0; k < K; k++) chunk_cap[k + 1] += chunk_cap[k];
-  bt->out_cap = chunk_cap[K];
-  bt->max_tgt = *std::max_element(tmax_tgt.begin(), tmax_tgt.end());
-  bt->max_tiers = *std::max_element(tmax_tiers.begin(), tmax_tiers.end());
+}
+
+// Stage 4: the pools concatenated in chunk order. Each chunk's bases are the prefix sums of
+// the pool sizes before it; the threads, chunk by chunk from a shared counter, give the
+// chunk's bindings their global class and result slots, rebase them and copy the chunk's
+// pools into place. False when the pools outgrow int32 offsets.
+// The rebasing relies on the bindings' slices [ip_beg, ip_end), [pr_beg, pr_end) and
+// [in_beg, in_end) being contiguous and partitioning the chunk's ipool, progs and instrs:
+// Packer::pack opens them at the pools' ends and closes them at its end, and a record's hit
+// appends at the ends. So shift_binding, per binding, touches every program and instruction
+// of the chunk exactly once. (-DKP_PACK_CHECK, the sanitizer builds, verifies it here.)
+void merge_chunk(PackCtx& c, int k) {
+  kp_batch* bt = c.bt;
+  Pools& q = c.pl[k];
+  const int32_t oi = (int32_t)c.bi[k], ol = (int32_t)c.bl[k], oo = (int32_t)c.bo[k], op = (int32_t)c.bp[k],
+                on = (int32_t)c.bn[k];
+  const std::vector<int32_t>& remap = c.remaps[c.owner[k]];
+  uint64_t off = c.chunk_cap[k];
+#ifdef KP_PACK_CHECK
+  int32_t ip_end = 0, pr_end = 0, in_end = 0;
+#endif
+  for (int i = c.lo[k]; i < c.lo[k + 1]; i++) {
+    BindHdr& h = bt->hdr[i];
+    bt->bcls[i] = bt->bcls[i] < 0 ? 0 : remap[bt->bcls[i]];
+    h.out_off = off;  // private result slots: no atomic on the emit path
+    off += h.out_cap;
+#ifdef KP_PACK_CHECK
+    if (h.ip_beg != ip_end || h.pr_beg != pr_end || h.in_beg != in_end) abort();
+    ip_end = h.ip_end, pr_end = h.pr_end, in_end = h.in_end;
+#endif
+    if (k == 0) continue;  // (its bases are zero)
+    shift_binding(h, q.ipool.data() + h.ip_beg, q.progs.data() + h.pr_beg, q.instrs.data() + h.in_beg, oi, ol, oo,
+                  op, on);
+  }
+#ifdef KP_PACK_CHECK
+  if ((size_t)ip_end != q.ipool.size() || (size_t)pr_end != q.progs.size() || (size_t)in_end != q.instrs.size()) abort();
+#endif
+  std::copy(q.ipool.begin(), q.ipool.end(), bt->ipool.begin() + (long)c.bi[k]);
+  std::copy(q.lpool.begin(), q.lpool.end(), bt->lpool.begin() + (long)c.bl[k]);
+  std::copy(q.tols.begin(), q.tols.end(), bt->tols.begin() + (long)c.bo[k]);
+  std::copy(q.progs.begin(), q.progs.end(), bt->progs.begin() + (long)c.bp[k]);
+  std::copy(q.instrs.begin(), q.instrs.end(), bt->instrs.begin() + (long)c.bn[k]);
+  q = Pools();
+}
+bool merge_chunks(PackCtx& c) {
+  kp_batch* bt = c.bt;
+  const int K = c.K;
+  for (int k = 0; k < K; k++) {
+    c.bi[k + 1] = c.bi[k] + c.pl[k].ipool.size();
+    c.bl[k + 1] = c.bl[k] + c.pl[k].lpool.size();
+    c.bo[k + 1] = c.bo[k] + c.pl[k].tols.size();
+    c.bp[k + 1] = c.bp[k] + c.pl[k].progs.size();
+    c.bn[k + 1] = c.bn[k] + c.pl[k].instrs.size();
+    c.chunk_cap[k + 1] += c.chunk_cap[k];
+  }
+  if (c.bi[K] > (size_t)INT32_MAX || c.bl[K] > (size_t)INT32_MAX || c.bo[K] > (size_t)INT32_MAX ||
+      c.bp[K] > (size_t)INT32_MAX || c.bn[K] > (size_t)INT32_MAX)
+    return false;  // pool offsets are int32
+  bt->ipool.resize(c.bi[K]);
+  bt->lpool.resize(c.bl[K]);
+  bt->tols.resize(c.bo[K]);
+  bt->progs.resize(c.bp[K]);
+  bt->instrs.resize(c.bn[K]);
+  bt->out_cap = c.chunk_cap[K];
+  bt->max_tgt = *std::max_element(c.tmax_tgt.begin(), c.tmax_tgt.end());
+  bt->max_tiers = *std::max_element(c.tmax_tiers.begin(), c.tmax_tiers.end());
   std::atomic<int> next_merge(0);
-  auto merge = [&](int) {
-    for (;;) {
-      const int k = next_merge.fetch_add(1);
-      if (k >= K) break;
-      Pools& q = pl[k];
-      const int32_t oi = (int32_t)bi[k], ol = (int32_t)bl[k], oo = (int32_t)bo[k], op = (int32_t)bp[k],
-                    on = (int32_t)bn[k];
-      const std::vector<int32_t>& remap = remaps[owner[k]];
-      uint64_t off = chunk_cap[k];
-      for (int i = lo[k]; i < lo[k + 1]; i++) {
-        BindHdr& h = bt->hdr[i];
-        bt->bcls[i] = bt->bcls[i] < 0 ? 0 : remap[bt->bcls[i]];
-        h.out_off = off;  // private result slots: no atomic on the emit path
-        off += h.out_cap;
-        if (k == 0) continue;
-        for (int j = 0; j < h.filt_cnt; j++) q.ipool[h.filt_off + j] += op;
-        for (int j = 0; j < h.ovf_cnt; j++) q.ipool[h.ovf_off + j] += op;
-        for (int j = 0; j < h.sw_cnt; j++) q.ipool[h.sw_off + j] += op;
-        h.tgt_off += oi, h.evict_off += oi, h.filt_off += oi, h.ovf_off += oi, h.sw_off += oi;
-        h.sreq_off += oi, h.mreq_off += oi, h.ip_beg += oi, h.ip_end += oi;
-        h.sw_w_off += ol, h.sreq_q_off += ol, h.mreq_q_off += ol;
-        h.tol_off += oo;
-        h.pr_beg += op, h.pr_end += op;
-        h.in_beg += on, h.in_end += on;
-      }
-      if (k > 0) {
-        for (Prog& p : q.progs) p.ins_off += on;
-        for (Instr& x : q.instrs) {
-          if (x.op == OP_EXCLUDE || x.op == OP_NAMES) x.a += oi;
-          else if (x.op == OP_LBL_IN || x.op == OP_LBL_NOTIN || x.op == OP_FLD_IN || x.op == OP_FLD_NOTIN ||
-                   x.op == OP_ZONE_IN || x.op == OP_ZONE_NOTIN)
-            x.b += oi;
+  c.on_threads([&](int) {
+    for (int k; (k = next_merge.fetch_add(1)) < K;) merge_chunk(c, k);
+  });
+  return true;
+}
+
+// Stage 5: the new records into the shards (thread t fills shards t, t + T, ...), and the
+// cache's counts.
+void fill_cache(PackCtx& c) {
+  kp_pack_cache* cache = c.cache;
+  if (!cache) return;
+  c.on_threads([&](int t) {
+    for (int sh = t; sh < kCacheShards; sh += c.T) {
+      PackTable& tab = cache->shard[sh];
+      for (int k = 0; k < c.K; k++)
+        for (PackRec*& r : c.newrecs[(size_t)k * kCacheShards + sh]) {
+          tab.put(r);
+          r = nullptr;
         }
-      }
-      std::copy(q.ipool.begin(), q.ipool.end(), bt->ipool.begin() + (long)bi[k]);
-      std::copy(q.lpool.begin(), q.lpool.end(), bt->lpool.begin() + (long)bl[k]);
-      std::copy(q.tols.begin(), q.tols.end(), bt->tols.begin() + (long)bo[k]);
-      std::copy(q.progs.begin(), q.progs.end(), bt->progs.begin() + (long)bp[k]);
-      std::copy(q.instrs.begin(), q.instrs.end(), bt->instrs.begin() + (long)bn[k]);
-      q = Pools();
     }
-  };
-  on_threads(merge);
-  if (cache) {  // the new records into the shards (thread t fills shards t, t + T, ...)
-    on_threads([&](int t) {
-      for (int sh = t; sh < kCacheShards; sh += T) {
-        PackTable& tab = cache->shard[sh];
-        for (int k = 0; k < K; k++)
-          for (PackRec*& r : newrecs[(size_t)k * kCacheShards + sh]) {
-            tab.put(r);
-            r = nullptr;
-          }
-      }
-    });
-    uint64_t h = 0;
-    for (uint64_t x : thits) h += x;
-    cache->hits += h;
-    cache->misses += (uint64_t)n - h;
-    cache->last_hits = h;
-  }
-  // a class's representative: its first binding
+  });
+  uint64_t h = 0;
+  for (uint64_t x : c.thits) h += x;
+  cache->hits += h;
+  cache->misses += (uint64_t)c.n - h;
+  cache->last_hits = h;
+}
+
+// Stage 6: a class's representative, its first binding.
+void pick_representatives(PackCtx& c) {
+  kp_batch* bt = c.bt;
   size_t left = bt->crep.size() - 1;
-  for (int i = 0; i < n && left; i++) {
+  for (int i = 0; i < c.n && left; i++) {
     const int32_t g = bt->bcls[i];
     if (g && bt->crep[g] < 0) {
       bt->crep[g] = i;
       left--;
     }
   }
-  if (kp_env_flag("KP_PACK_TIMING")) {
-    auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    fprintf(stderr, "pack_parallel: %d threads, %d chunks, pack %.1f ms, merge+classes %.1f ms; per thread", T, K,
-            ms(tq0, tq1), ms(tq1, std::chrono::steady_clock::now()));
-    for (double x : tms) fprintf(stderr, " %.1f", x);
-    fprintf(stderr, "; started at");
-    for (double x : tstart) fprintf(stderr, " %.1f", x);
-    fprintf(stderr, "\n");
+}
+
+// KP_PACK_TIMING: the pack stage, and everything after it up to this call.
+void report_timing(const PackCtx& c) {
+  auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+  fprintf(stderr, "pack_parallel: %d threads, %d chunks, pack %.1f ms, merge+classes %.1f ms; per thread", c.T, c.K,
+          ms(c.tq0, c.tq1), ms(c.tq1, PackClock::now()));
+  for (double x : c.tms) fprintf(stderr, " %.1f", x);
+  fprintf(stderr, "; started at");
+  for (double x : c.tstart) fprintf(stderr, " %.1f", x);
+  fprintf(stderr, "\n");
 #ifdef KP_PACK_PROF
-    fprintf(stderr, "pack sections (Mcycles, cumulative): gvk %.1f targets %.1f tolerations %.1f affinity %.1f "
-            "static %.1f requests %.1f rest %.1f\n", g_pack_cyc[0] / 1e6, g_pack_cyc[1] / 1e6, g_pack_cyc[2] / 1e6,
-            g_pack_cyc[3] / 1e6, g_pack_cyc[4] / 1e6, g_pack_cyc[5] / 1e6, g_pack_cyc[6] / 1e6);
+  fprintf(stderr, "pack sections (Mcycles, cumulative): gvk %.1f targets %.1f tolerations %.1f affinity %.1f "
+          "static %.1f requests %.1f rest %.1f\n", g_pack_cyc[0] / 1e6, g_pack_cyc[1] / 1e6, g_pack_cyc[2] / 1e6,
+          g_pack_cyc[3] / 1e6, g_pack_cyc[4] / 1e6, g_pack_cyc[5] / 1e6, g_pack_cyc[6] / 1e6);
 #endif
-  }
+}
+
+bool pack_parallel(kp_snapshot* s, const kp_binding* bindings, int n, kp_batch* bt, const kp_binding_key* keys,
+                   kp_pack_cache* cache, const int32_t* row_of) {
+  const int T = std::max(1, std::min((int)kp_env_int("KP_PACK_THREADS", host_cpus()), n / 4096));
+  PackCtx c(s, bindings, n, bt, keys, cache, row_of, T);
+  prepare_cache(c);
+  if (!pack_chunks(c)) return false;
+  unify_classes(c);
+  if (!merge_chunks(c)) return false;
+  fill_cache(c);
+  pick_representatives(c);
+  if (kp_env_flag("KP_PACK_TIMING")) report_timing(c);
   return true;
 }
+}  // namespace
 
 // Bindings per estimator class below which a batch skips the class orders.
 static int64_t order_amort() {  // (read per batch: tests switch it)
   return std::max<int64_t>(0, kp_env_int("KP_ORDER_AMORT", 4));
 }
+
+extern "C" {
 
 int kp_batch_create_filters(kp_engine* e, const kp_snapshot* sc, const kp_binding* bindings, const kp_binding_key* keys,
                             uint64_t n, kp_pack_cache* cache, const kp_estimates* est, const kp_filter_answers* flt,

@@ -11,7 +11,8 @@
 // more than four tolerations, spec.Clusters members with eviction tasks) through
 // the bitset filter, every (binding, cluster) pair against the oracle's filter.
 // run_affinity_answers runs kp_schedule_affinities_ex with both answers (rows shared by the
-// rounds' batches), run_batch_answers one batch created with both and scheduled twice.
+// rounds' batches), run_batch_answers one batch created with both and scheduled twice,
+// run_pack_stages the packer on two threads with keyed creations and one that fails.
 // Exit code 0 = no mismatch (the sanitizers abort on their own findings).
 #include <algorithm>
 #include <cstdio>
@@ -516,6 +517,92 @@ static int run_batch_answers(kp_engine* e) {
   return bad ? 1 : 0;
 }
 
+// The packer's stages on more than one thread (pack.cpp): 8 193 bindings are nine chunks on two
+// packing threads (KP_PACK_THREADS=4, one per 4096 bindings at most). A keyed cold creation
+// makes every record and the threads fill the cache's shards; a warm one with every tenth
+// generation moved mixes hits and misses inside each chunk; both images must equal the unkeyed
+// one (kp_batch_digest). Then a creation that fails after the chunks are packed (a component-set
+// binding with 17 components): its new records were never handed to the cache and must be
+// freed with the call (the leak check), the cache stays empty and usable.
+static int run_pack_stages(kp_engine* e) {
+  kps_world* w = nullptr;
+  const uint32_t C = 130;
+  if (kps_create(6, 21, C, 0, 8193, &w)) return 1;
+  uint64_t nc = 0, nb = 0;
+  const kp_cluster* cl = kps_clusters(w, &nc);
+  const kp_binding* bs = kps_bindings(w, &nb);
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.multiple_pod_templates_scheduling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  setenv("KP_PACK_THREADS", "4", 1);
+  std::vector<kp_binding_key> cold(nb), warm(nb);
+  for (uint64_t i = 0; i < nb; i++) {
+    cold[i] = kp_binding_key{bs[i].uid, (int64_t)(1 + i % 5)};
+    warm[i] = kp_binding_key{bs[i].uid, cold[i].generation + (i % 10 == 3)};
+  }
+  kp_snapshot* s = nullptr;
+  kp_pack_cache* cache = nullptr;
+  int bad = 0;
+  uint64_t dig[3] = {0, 1, 2};
+  kp_pack_cache_stats st{};
+  if (kp_snapshot_create(e, cl, nc, &o, &s) || kp_pack_cache_create(0, &cache)) {
+    fprintf(stderr, "pack stages: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  }
+  for (int form = 0; form < 3 && !bad; form++) {
+    kp_batch* b = nullptr;
+    const int rc = form == 0 ? kp_batch_create(e, s, bs, nb, &b)
+                             : kp_batch_create_keyed(e, s, bs, form == 1 ? cold.data() : warm.data(), nb, cache, &b);
+    if (rc || kp_batch_digest(b, &dig[form])) {
+      fprintf(stderr, "pack stages: form %d: engine error: %s\n", form, kp_last_error(e));
+      bad++;
+    }
+    if (b) kp_batch_destroy(b);
+    kp_pack_cache_get_stats(cache, &st);
+    const uint64_t want_hits = form == 2 ? nb - (nb + 6) / 10 : 0;
+    if (form && st.last_hits != want_hits && bad++ < 3)
+      fprintf(stderr, "pack stages: form %d: %llu hits, expected %llu\n", form, (unsigned long long)st.last_hits,
+              (unsigned long long)want_hits);
+  }
+  if (dig[1] != dig[0] || dig[2] != dig[0]) bad++;
+  // the failing creation, against a cache of its own
+  if (!bad) {
+    std::vector<kp_binding> broken(bs, bs + nb);
+    std::vector<kp_component> comps(17);
+    for (auto& c : comps) c = kp_component{}, c.replicas = 1;
+    kp_spread_constraint sc{};
+    const std::string fld = "cluster";
+    sc.spread_by_field = kp_str{fld.data(), (uint32_t)fld.size()};
+    sc.min_groups = sc.max_groups = 1;
+    kp_binding& x = broken[nb / 2];
+    x.components = comps.data();
+    x.n_components = (uint32_t)comps.size();
+    x.spread_constraints = &sc;
+    x.n_spread_constraints = 1;
+    kp_pack_cache* c2 = nullptr;
+    kp_batch* b = nullptr;
+    if (kp_pack_cache_create(0, &c2)) bad++;
+    const int rc = c2 ? kp_batch_create_keyed(e, s, broken.data(), cold.data(), nb, c2, &b) : 0;
+    if (rc != KP_ENOTSUP && bad++ < 3) fprintf(stderr, "pack stages: the 17-component binding gave rc %d\n", rc);
+    if (c2) kp_pack_cache_get_stats(c2, &st);
+    if (st.entries != 0) bad++;
+    if (b) kp_batch_destroy(b);
+    b = nullptr;
+    // the same cache takes the sound bindings afterwards
+    if (c2 && (kp_batch_create_keyed(e, s, bs, cold.data(), nb, c2, &b) || kp_batch_digest(b, &dig[1]) || dig[1] != dig[0])) bad++;
+    if (b) kp_batch_destroy(b);
+    if (c2) kp_pack_cache_destroy(c2);
+  }
+  unsetenv("KP_PACK_THREADS");
+  if (cache) kp_pack_cache_destroy(cache);
+  if (s) kp_snapshot_destroy(s);
+  kps_destroy(w);
+  printf("pack stages: %llu bindings x %u clusters, unkeyed / cold / warm digests %s, %d mismatches\n",
+         (unsigned long long)nb, C, dig[1] == dig[0] && dig[2] == dig[0] ? "equal" : "DIFFER", bad);
+  return bad ? 1 : 0;
+}
+
 // `driver ceiling`: the snapshots at which a workgroup's LDS is full (tests/test_lds_ceiling.py:
 // 18 624 clusters without spread bindings, 14 336 with them, and the class-order switch at
 // 16 384 / 16 385) instead of the small universes, so the sanitizer sees every global array
@@ -537,6 +624,7 @@ int main(int argc, char** argv) {
   if (!ceiling) fails += run_filter_shapes(e);
   if (!ceiling) fails += run_affinity_answers(e);
   if (!ceiling) fails += run_batch_answers(e);
+  if (!ceiling) fails += run_pack_stages(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
