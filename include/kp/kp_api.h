@@ -41,6 +41,8 @@
  *        kp_snapshot_create         <- cache.Cache.Snapshot (pkg/scheduler/cache/cache.go:124-139)
  *        kp_schedule_affinities     <- Scheduler.scheduleResourceBindingWithClusterAffinities
  *                                      (pkg/scheduler/scheduler.go:584-585,618-684)
+ *        kp_affected_bindings       <- Scheduler.enqueueAffectedBindings / enqueueAffectedCRBs
+ *                                      (pkg/scheduler/event_handler.go:400-491)
  *
  * Return convention: 0 = OK, <0 = KP_E* ; kp_last_error() gives the text.
  * No exceptions cross the ABI. An engine handle is not re-entrant.
@@ -466,6 +468,55 @@ void kp_snapshot_destroy(kp_snapshot* s);
  * clusters needs kp_snapshot_create. */
 int kp_snapshot_update(kp_engine* e, kp_snapshot* s, const kp_cluster* clusters, uint64_t n_clusters,
                        int* dict_grew);
+/* ---- which bindings a cluster event affects ---------------------------------------------
+ * reconcileCluster (pkg/scheduler/event_handler.go:388-397) lists every ResourceBinding and
+ * ClusterResourceBinding per cluster object and requeues those whose current affinity matches
+ * it (enqueueAffectedBindings / enqueueAffectedCRBs, event_handler.go:400-491). A kp_watch
+ * holds, per binding, the compiled selector of the one affinity those loops read;
+ * kp_affected_bindings answers for a set of clusters at once, on the device.
+ *
+ * Binding i of a watch, by mode[i] (mode == NULL: every binding KP_WATCH_MATCH):
+ *   KP_WATCH_SKIP    never listed. For the bindings the loops skip: another scheduler's name
+ *                    (schedulerNameFilter) or suspended scheduling; kp_binding carries neither.
+ *   KP_WATCH_ALWAYS  listed whenever n_clusters > 0. For a ClusterAffinities binding whose
+ *                    Status.SchedulerObservedGeneration differs from its Generation
+ *                    (event_handler.go:419-426).
+ *   KP_WATCH_MATCH   the affinity is cluster_affinities[getAffinityIndex(observed_affinity_name)]
+ *                    .affinity when n_cluster_affinities > 0 (tested first, as the reference
+ *                    does; index 0 for an empty or unknown name, helper.go:99-110), else
+ *                    cluster_affinity when has_cluster_affinity, else nil. Nil: listed.
+ *                    Otherwise listed exactly when util.ClusterMatches holds for at least one of
+ *                    the listed clusters in the snapshot's current state.
+ * Nothing else plays a part: not the term's overflow affinities, tolerations, the GVK, spread
+ * constraints, eviction tasks, spec.Clusters, kp_options.enabled_plugins or the cluster's
+ * deleting flag (a batch's filter reads all of these, so a kp_batch cannot answer this).
+ *
+ * The watch remembers its snapshot and the state of the snapshot's dictionaries:
+ * kp_affected_bindings returns KP_ESTATE (kp_last_error says why) with another snapshot, and
+ * after a kp_snapshot_update on it that reported dict_grew = 1; an update with dict_grew = 0
+ * leaves the watch valid. One event batch is: kp_affected_bindings over the old state,
+ * kp_snapshot_update, a new watch if dict_grew, kp_affected_bindings over the new state, the
+ * union of both lists to the queue (the reference adds the old and the new object,
+ * event_handler.go:351-352, and the queue dedups).
+ * n_bindings must be below 2^31 (KP_EINVAL). Nothing of `bindings` is retained. */
+typedef struct kp_watch kp_watch;
+enum { KP_WATCH_MATCH = 0, KP_WATCH_ALWAYS = 1, KP_WATCH_SKIP = 2 };
+/* mode may be NULL (all KP_WATCH_MATCH). */
+int kp_watch_create(kp_engine* e, const kp_snapshot* s, const kp_binding* bindings, uint64_t n_bindings,
+                    const uint8_t* mode, kp_watch** out);
+void kp_watch_destroy(kp_watch* w);
+typedef struct kp_affected {
+  uint64_t n;
+  const uint32_t* bindings; /* ascending, distinct; engine-owned until the next call on the engine */
+} kp_affected;
+/* The watch's bindings that the clusters cluster_idx[0, n_clusters) affect (caller indices as
+ * given to kp_snapshot_create; repeats allowed). KP_EINVAL for an index at or beyond the
+ * snapshot's cluster count and for a null pointer; n_clusters == 0 gives an empty list and
+ * launches nothing. Under kp_engine_set_profile the call's launches are what
+ * kp_last_kernel_times reports. */
+int kp_affected_bindings(kp_engine* e, const kp_watch* w, const kp_snapshot* s, const uint32_t* cluster_idx,
+                         uint64_t n_clusters, kp_affected* out);
+
 /* Packed snapshot as one relocatable byte image (for RCCL broadcast) and back. */
 int kp_snapshot_export(const kp_snapshot* s, const void** bytes, uint64_t* n_bytes);
 int kp_snapshot_import(kp_engine* e, const void* bytes, uint64_t n_bytes, kp_snapshot** out);

@@ -184,6 +184,17 @@ class kp_fit_diagnosis(C.Structure):
 TAINT_REF_CLUSTER_BITS = 18  # taint_ref = caller cluster index | taint index << 18
 
 
+class kp_affected(C.Structure):
+    """kp_affected_bindings: the watch's bindings a set of clusters affects, ascending."""
+    _fields_ = [("n", u64), ("bindings", C.POINTER(u32))]
+
+
+# kp_watch_create's mode per binding (enqueueAffectedBindings, event_handler.go:400-444)
+WATCH_MATCH = 0   # listed when its current affinity is nil or matches a changed cluster
+WATCH_ALWAYS = 1  # listed on every event (ClusterAffinities, observed generation behind)
+WATCH_SKIP = 2    # never listed (another scheduler's name, suspended scheduling)
+
+
 class kp_results_packed(C.Structure):
     """kp_results in 4 bytes per target: targets[i] = cluster index | replicas << 16, the
     replicas 0xFFFF when outside 0..65534 and then the next entry of wide_replicas

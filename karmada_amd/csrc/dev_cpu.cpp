@@ -403,6 +403,23 @@ int hist_write(stream_t, int n, int U, const uint32_t* uid_ref, const uint32_t* 
   });
 }
 
+int affected(stream_t, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* cw_word,
+             const uint64_t* cw_mask, int n_cw, uint32_t* cnt) {
+  return grid("k_affected", bv.B, 0, [&](int b, unsigned char*) {
+    body_affected(CpuBlk{nullptr}, b, s, bv, wprog, cw_word, cw_mask, n_cw, cnt);
+  });
+}
+int affected_rows(stream_t, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* ranks, int n,
+                  uint32_t* cnt) {
+  return grid("k_affected_rows", bv.B, 0, [&](int b, unsigned char*) {
+    body_affected_rows(CpuBlk{nullptr}, b, s, bv, wprog, ranks, n, cnt);
+  });
+}
+int affected_write(stream_t, int n, const uint32_t* cnt, const uint64_t* offsets, uint32_t* out) {
+  for (int b = 0; b < n; b++) body_affected_write(b, cnt, offsets, out);
+  return 0;
+}
+
 int offsets(stream_t, const int32_t* status, const uint32_t* count, int n, uint64_t* off, uint64_t* part) {
   int64_t red[8];
   const int nb = (n + kOffChunk - 1) / kOffChunk;

@@ -1,7 +1,7 @@
 // engine.cpp — host side of the kp placement engine: kp_engine_* and the schedule, filter,
 // score, diagnosis and component-set entry points of include/kp/kp_api.h (the snapshots are in
 // snapshot.cpp, the binding packer and batch creation in pack.cpp, the node estimator in
-// nodes.cpp). Kernel orchestration on the engine's HIP streams, the host-kept selectGroups
+// nodes.cpp, the cluster-event watch in watch.cpp). Kernel orchestration on the engine's HIP streams, the host-kept selectGroups
 // step, and the one definition of kp_host.h's shared state.
 #include "kp_host.h"
 #include "kp_paths.h"
@@ -218,6 +218,7 @@ void kp_engine_destroy(kp_engine* e) {
   for (auto& ev : e->ev)
     if (ev) dev::event_destroy(ev);
   for (auto& ev : e->pev) dev::event_destroy(ev);
+  buf_pool().put(-1, e->affected.h, e->affected.bytes);
   // (aliases: KP_STREAMS < 3)
   if (e->stream3 && e->stream3 != e->stream2 && e->stream3 != e->stream) dev::stream_destroy(e->stream3);
   if (e->stream2 && e->stream2 != e->stream) dev::stream_destroy(e->stream2);
@@ -301,9 +302,12 @@ static int ensure_packed(kp_engine* e, kp_batch* bt) {
   return 0;
 }
 
+}  // extern "C"
+
 // Per-kernel profiling (kp_engine_set_profile): prof_begin records the start event of
-// launch i on its stream, prof_end its end event and what it covered.
-static int prof_begin(kp_engine* e, dev::stream_t st) {
+// launch i on its stream, prof_end its end event and what it covered (kp_host.h: watch.cpp
+// records its launches through the same three).
+int prof_begin(kp_engine* e, dev::stream_t st) {
   if (!e->prof) return -1;
   const size_t i = e->pk.size();
   while (e->pev.size() < 2 * i + 2) {
@@ -315,13 +319,13 @@ static int prof_begin(kp_engine* e, dev::stream_t st) {
   e->pk.push_back({"", 0, -1});
   return (int)i;
 }
-static void prof_end(kp_engine* e, int i, dev::stream_t st, const char* name, uint64_t units, int units_stat = -1) {
+void prof_end(kp_engine* e, int i, dev::stream_t st, const char* name, uint64_t units, int units_stat) {
   if (i < 0) return;
   (void)dev::event_record(e->pev[2 * (size_t)i + 1], st);
   e->pk[i] = {name, units, units_stat};
 }
 // After the batch's final sync: each kernel's launches folded by name.
-static void prof_fold(kp_engine* e, const uint32_t* h_stats) {
+void prof_fold(kp_engine* e, const uint32_t* h_stats) {
   e->ktimes.clear();
   for (size_t i = 0; i < e->pk.size(); i++) {
     const auto& k = e->pk[i];
@@ -341,12 +345,9 @@ static void prof_fold(kp_engine* e, const uint32_t* h_stats) {
   }
   e->pk.clear();
 }
-#define KPROF(ST, NAME, UNITS, STAT, CALL)           \
-  do {                                               \
-    const int pi_ = prof_begin(e, ST);               \
-    HIPCHK(CALL);                                    \
-    prof_end(e, pi_, ST, NAME, (uint64_t)(UNITS), STAT); \
-  } while (0)
+
+extern "C" {
+
 // launch names of the select kernels (kernels.hip picks the wide instance past half
 // the CU's LDS, as here)
 static const char* sel_name(int which, size_t smem) {

@@ -577,6 +577,48 @@ extern "C" __global__ void __launch_bounds__(64 * kFitHistWaves) k_hist_write(in
 #else
 ;
 #endif
+// kp_affected_bindings: one wave64 per watched binding, kAffectedWaves per workgroup, the
+// binding index through a scalar register as k_filter. k_affected over the snapshot's bitset
+// rows, k_affected_rows over the per-pair evaluator; then k_offsets_a / _b over cnt and
+// k_affected_write, one thread per binding.
+constexpr int kAffectedWaves = 4;
+extern "C" __global__ void __launch_bounds__(64 * kAffectedWaves) k_affected(SnapView s, BatchView bv,
+                                                                           const int32_t* wprog,
+                                                                           const int32_t* cw_word,
+                                                                           const uint64_t* cw_mask, int n_cw,
+                                                                           uint32_t* cnt)
+#if KP_K(8)
+{
+  const int b = (int)(blockIdx.x * kAffectedWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (b >= bv.B) return;  // wave-uniform
+  body_affected(WaveBlk{nullptr}, b, s, bv, wprog, cw_word, cw_mask, n_cw, cnt);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kAffectedWaves) k_affected_rows(SnapView s, BatchView bv,
+                                                                                const int32_t* wprog,
+                                                                                const int32_t* ranks, int n,
+                                                                                uint32_t* cnt)
+#if KP_K(8)
+{
+  const int b = (int)(blockIdx.x * kAffectedWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (b >= bv.B) return;  // wave-uniform
+  body_affected_rows(WaveBlk{nullptr}, b, s, bv, wprog, ranks, n, cnt);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(256) k_affected_write(int n, const uint32_t* cnt, const uint64_t* offsets,
+                                                                   uint32_t* out)
+#if KP_K(8)
+{
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b < n) body_affected_write(b, cnt, offsets, out);
+}
+#else
+;
+#endif
 extern "C" __global__ void __launch_bounds__(kOffThreads) k_offsets_a(const int32_t* status, const uint32_t* count, int n,
                                                                     uint64_t* offsets, uint64_t* part)
 #if KP_K(8)
@@ -1041,6 +1083,27 @@ int hist_write(stream_t st, int n, int U, const uint32_t* uid_ref, const uint32_
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_hist_write, hist_grid(n), dim3(64 * kFitHistWaves), 0, (hipStream_t)st, n, U, uid_ref, dense,
                      offsets, reason, taint_ref, count, n_fit, n_del);
+  return chk(hipGetLastError());
+}
+
+static dim3 affected_grid(int n) { return dim3((n + kAffectedWaves - 1) / kAffectedWaves); }
+int affected(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* cw_word,
+             const uint64_t* cw_mask, int n_cw, uint32_t* cnt) {
+  if (bv.B <= 0) return 0;
+  hipLaunchKernelGGL(k_affected, affected_grid(bv.B), dim3(64 * kAffectedWaves), 0, (hipStream_t)st, s, bv, wprog,
+                     cw_word, cw_mask, n_cw, cnt);
+  return chk(hipGetLastError());
+}
+int affected_rows(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* ranks,
+                  int n, uint32_t* cnt) {
+  if (bv.B <= 0) return 0;
+  hipLaunchKernelGGL(k_affected_rows, affected_grid(bv.B), dim3(64 * kAffectedWaves), 0, (hipStream_t)st, s, bv, wprog,
+                     ranks, n, cnt);
+  return chk(hipGetLastError());
+}
+int affected_write(stream_t st, int n, const uint32_t* cnt, const uint64_t* offsets, uint32_t* out) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_affected_write, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)st, n, cnt, offsets, out);
   return chk(hipGetLastError());
 }
 

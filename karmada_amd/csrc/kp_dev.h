@@ -154,6 +154,17 @@ int reason_hist(stream_t st, const SnapView& s, const uint32_t* words, int n, ui
 int hist_count(stream_t st, int n, int U, const uint32_t* dense, uint32_t* nbins);
 int hist_write(stream_t st, int n, int U, const uint32_t* uid_ref, const uint32_t* dense, const uint64_t* offsets,
                uint32_t* reason, uint32_t* taint_ref, uint32_t* count, uint32_t* n_fit, uint32_t* n_del);
+// kp_affected_bindings over a watch's bv.B bindings (bv: progs / instrs / ipool only; wprog[b]
+// a program id, kWatchAlways or kWatchNever): cnt[b] = 1 when binding b's affinity matches one
+// of the changed clusters. affected (body_affected; requires s.n_bits > 0): the clusters as
+// n_cw distinct words cw_word[j] < s.W with their bits cw_mask[j]; affected_rows
+// (body_affected_rows): as n distinct ranks < s.C. affected_write: the listed bindings'
+// indices at offsets[b] (the scan of cnt), ascending.
+int affected(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* cw_word,
+             const uint64_t* cw_mask, int n_cw, uint32_t* cnt);
+int affected_rows(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* wprog, const int32_t* ranks,
+                  int n, uint32_t* cnt);
+int affected_write(stream_t st, int n, const uint32_t* cnt, const uint64_t* offsets, uint32_t* out);
 // CSR offsets[n + 1] of the per-binding results (counts of OK bindings), on the device;
 // part: ceil(n / kOffChunk) u64 of scratch.
 int offsets(stream_t st, const int32_t* status, const uint32_t* count, int n, uint64_t* off, uint64_t* part);

@@ -352,4 +352,55 @@ KP_UNROLL
   }
 }
 
+// k_affected (kp_affected_bindings): the transposed question of the filter, "does the one
+// affinity enqueueAffectedBindings reads for binding b (event_handler.go:417-431) match any of
+// a few changed clusters", by the calling wave. wprog[b] is that affinity's program in the
+// watch's pools (bv holds progs / instrs / ipool only), kWatchAlways for a nil affinity or a
+// binding listed on every event, kWatchNever for one never listed. b is wave-uniform, so
+// wprog[b] and the program walk are scalar loads as in body_filter. cnt[b] = 1 when listed.
+// util.ClusterMatches alone decides: BR_BASE (the not-deleting row of findClustersThatFit) is
+// not ANDed, and cw_mask carries bits of real clusters only, which clears what the negated
+// rows set past C.
+// Over the snapshot's bitset rows: the changed clusters as n_cw distinct 64-cluster words
+// (cw_word[j] < W, cw_mask[j] their bits), one lane per changed word; the loop leaves
+// wave-uniformly at the first word that holds a match.
+template <class BLK>
+KP_FI void body_affected(const BLK& B, int b, const SnapView& s, const BatchView& bv, const int32_t* wprog,
+                         const int32_t* cw_word, const uint64_t* cw_mask, int n_cw, uint32_t* cnt) {
+  const int32_t p = kp_ldu(wprog + b);
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  bool hit = p == kWatchAlways;
+  if (p >= 0) {
+    for (int j0 = 0; j0 < n_cw && !hit; j0 += ww) {  // (wave-uniform trip count: the ballot)
+      const int j = j0 + lane;
+      uint64_t m = 0;
+      if (j < n_cw) m = prog_word(s, bv, p, cw_word[j]) & cw_mask[j];
+      hit = B.wballot(m != 0) != 0;
+    }
+  }
+  if (lane == 0) cnt[b] = hit ? 1u : 0u;
+}
+// Without the bitset rows (or under KP_PAIR_ROWS=1): the changed clusters as n distinct ranks
+// (each < C), one lane per changed cluster through the per-pair evaluator.
+template <class BLK>
+KP_FI void body_affected_rows(const BLK& B, int b, const SnapView& s, const BatchView& bv, const int32_t* wprog,
+                              const int32_t* ranks, int n, uint32_t* cnt) {
+  const int32_t p = kp_ldu(wprog + b);
+  const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+  bool hit = p == kWatchAlways;
+  if (p >= 0) {
+    for (int j0 = 0; j0 < n && !hit; j0 += ww) {  // (wave-uniform trip count: the ballot)
+      const int j = j0 + lane;
+      const bool m = j < n && prog_match(s, bv, p, ranks[j]);
+      hit = B.wballot(m) != 0;
+    }
+  }
+  if (lane == 0) cnt[b] = hit ? 1u : 0u;
+}
+// k_affected_write: after the offsets scan over cnt, a listed binding's index at its offset
+// (one thread per binding), so the list is ascending and distinct by construction.
+KP_HD inline void body_affected_write(int b, const uint32_t* cnt, const uint64_t* offsets, uint32_t* out) {
+  if (cnt[b]) out[offsets[b]] = (uint32_t)b;
+}
+
 }  // namespace kp

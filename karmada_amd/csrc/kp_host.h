@@ -419,7 +419,28 @@ struct kp_engine {
   std::vector<dev::event_t> pev;
   std::vector<KProf> pk;
   std::vector<kp_kernel_time> ktimes;
+  // kp_affected_bindings' result: one page-locked block from the host pool, the list's
+  // length (8 bytes) and then the list, kept until the next call needs a larger one
+  struct {
+    uint64_t* h = nullptr;
+    size_t bytes = 0;
+  } affected;
 };
+
+// Per-kernel profiling (engine.cpp): prof_begin records the start event of a launch on its
+// stream (-1: profiling off), prof_end its end event, name and units; prof_fold, after the
+// call's final sync, folds the launches by name into kp_engine::ktimes (h_stats: the batch's
+// counters for launches whose units are device-side, or null when none is). A call clears
+// kp_engine::pk before its first launch.
+int prof_begin(kp_engine* e, dev::stream_t st);
+void prof_end(kp_engine* e, int i, dev::stream_t st, const char* name, uint64_t units, int units_stat = -1);
+void prof_fold(kp_engine* e, const uint32_t* h_stats);
+#define KPROF(ST, NAME, UNITS, STAT, CALL)               \
+  do {                                                   \
+    const int pi_ = prof_begin(e, ST);                   \
+    HIPCHK(CALL);                                        \
+    prof_end(e, pi_, ST, NAME, (uint64_t)(UNITS), STAT); \
+  } while (0)
 
 struct kp_snapshot {
   kp_engine* e = nullptr;

@@ -75,6 +75,9 @@ struct Instr {
 struct Prog {
   int32_t ins_off, ins_cnt;
 };
+// A watch's per-binding entry (kp_watch, k_affected) where it is no program id: the binding
+// is listed on every event, or on none.
+constexpr int32_t kWatchAlways = -1, kWatchNever = -2;
 
 // ---- binding header -----------------------------------------------------------
 enum : uint32_t {

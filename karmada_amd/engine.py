@@ -13,6 +13,9 @@ Mirrors (reference file:line):
                              <- estimator.ReplicaEstimator.MaxAvailableReplicas
                                  (pkg/estimator/client/interface.go:34-37) via
                                  calAvailableReplicas (core/util.go:56-118)
+  Watch.affected / GenericScheduler.affected_bindings
+                             <- Scheduler.enqueueAffectedBindings / enqueueAffectedCRBs
+                                 (pkg/scheduler/event_handler.go:400-491)
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ EXPORTS = (
     "kp_schedule_affinities", "kp_schedule_affinities_ex", "kp_filter_batch", "kp_filter_reasons", "kp_fit_diagnosis_batch", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
+    "kp_watch_create", "kp_watch_destroy", "kp_affected_bindings",
     "kp_multi_create", "kp_multi_destroy", "kp_multi_last_error", "kp_multi_devices", "kp_multi_engine",
     "kp_multi_snapshot_create", "kp_multi_snapshot_update", "kp_multi_snapshot_destroy", "kp_multi_snapshot_replica",
     "kp_multi_shard_cuts", "kp_multi_batch_create", "kp_multi_batch_destroy", "kp_multi_batch_shards",
@@ -118,6 +122,9 @@ def load_library(path: str = LIB_PATH):
     L.kp_engine_set_profile.argtypes = [vp, C.c_int]
     L.kp_last_kernel_times.argtypes = [vp, C.POINTER(api.kp_kernel_time), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kp_snapshot_replicate.argtypes = [vp, vp, C.POINTER(vp)]
+    L.kp_watch_create.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(vp)]
+    L.kp_watch_destroy.argtypes = [vp]
+    L.kp_affected_bindings.argtypes = [vp, vp, vp, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(api.kp_affected)]
     L.kp_multi_create.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]
     L.kp_multi_destroy.argtypes = [vp]
     L.kp_multi_last_error.restype = C.c_char_p
@@ -503,6 +510,64 @@ class Batch:
                                      r.n_bindings)
 
 
+class Watch:
+    """The bindings a cluster event can affect (kp_watch): per binding the compiled selector
+    of the one affinity enqueueAffectedBindings / enqueueAffectedCRBs evaluate
+    (pkg/scheduler/event_handler.go:400-491). modes: api.WATCH_* per binding (None: all
+    WATCH_MATCH). A watch answers for the snapshot it was made over until a Snapshot.update
+    on it returns True (the dictionaries grew): then make a new one."""
+
+    def __init__(self, snap: Snapshot, bindings: Sequence[dict] = (), structs=None,
+                 modes: Optional[Sequence[int]] = None):
+        self.snap = snap
+        eng = snap.engine
+        if structs is None:
+            w = api.World()
+            ba, n = w.bindings(bindings)
+        else:
+            ba, n = structs
+        self.n = n
+        marr = None
+        if modes is not None:
+            if len(modes) != n:
+                raise ValueError(f"modes has {len(modes)} entries for {n} bindings")
+            marr = (C.c_uint8 * max(1, n))(*modes)
+        h = C.c_void_p()
+        eng._check(eng.L.kp_watch_create(eng.h, snap.h, ba, n, marr, C.byref(h)), "kp_watch_create")
+        self.h = h
+
+    def affected_raw(self, idx: Sequence[int], snap: Optional[Snapshot] = None) -> api.kp_affected:
+        """kp_affected_bindings over caller cluster indices (a sequence, or a ctypes c_uint32
+        array): the engine's list, valid until the next call on the engine. snap: the snapshot
+        to answer over (default: the watch's own)."""
+        eng = self.snap.engine
+        out = api.kp_affected()
+        arr = idx if isinstance(idx, C.Array) else (C.c_uint32 * max(1, len(idx)))(*idx)
+        eng._check(eng.L.kp_affected_bindings(eng.h, self.h, (snap or self.snap).h, arr, len(idx), C.byref(out)),
+                   "kp_affected_bindings")
+        return out
+
+    def affected(self, clusters: Sequence) -> List[int]:
+        """The indices of the bindings to requeue for the changed clusters (names or caller
+        indices, repeats allowed) in the snapshot's current state, ascending."""
+        if any(isinstance(c, str) for c in clusters):
+            pos = {n: i for i, n in enumerate(self.snap.names)}
+            clusters = [pos[c] if isinstance(c, str) else c for c in clusters]
+        r = self.affected_raw([int(c) for c in clusters])
+        return [int(r.bindings[i]) for i in range(r.n)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.snap.engine.L.kp_watch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MultiEngine:
     """One scheduler process over N GPUs (kp_multi): an engine per device, the snapshot
     replicated device to device, each batch sharded by cost across the devices and
@@ -690,6 +755,16 @@ class GenericScheduler:
             out.append([self.snapshot.names[c] for c in range(C_) if (m[i * W + (c >> 6)] >> (c & 63)) & 1])
         b.close()
         return out
+
+    def affected_bindings(self, bindings: Sequence[dict], changed: Sequence,
+                          modes: Optional[Sequence[int]] = None) -> List[int]:
+        """enqueueAffectedBindings (event_handler.go:400-444) for the changed clusters (names
+        or indices) at once: the indices of the bindings to requeue, ascending (Watch)."""
+        w = Watch(self.snapshot, bindings, modes=modes)
+        try:
+            return w.affected(changed)
+        finally:
+            w.close()
 
     def filter_reasons(self, bindings: Sequence[dict], filters=None) -> List[List[int]]:
         """kp_filter_reasons: the KP_REASON_* word of every (binding, cluster) pair; filters:

@@ -12,7 +12,8 @@
 // the bitset filter, every (binding, cluster) pair against the oracle's filter.
 // run_affinity_answers runs kp_schedule_affinities_ex with both answers (rows shared by the
 // rounds' batches), run_batch_answers one batch created with both and scheduled twice,
-// run_pack_stages the packer on two threads with keyed creations and one that fails.
+// run_pack_stages the packer on two threads with keyed creations and one that fails,
+// run_watch one kp_watch and kp_affected_bindings in both modes.
 // Exit code 0 = no mismatch (the sanitizers abort on their own findings).
 #include <algorithm>
 #include <cstdio>
@@ -603,6 +604,79 @@ static int run_pack_stages(kp_engine* e) {
   return bad ? 1 : 0;
 }
 
+// kp_watch_create and kp_affected_bindings (watch.cpp) over a universe with multi-term
+// bindings: one watch with all three modes, one call over the bitset rows and one under
+// KP_PAIR_ROWS=1 with a changed set that repeats an index and ends in the partial last word,
+// every binding against enqueueAffectedBindings restated over the oracle's ClusterMatches;
+// then a watch made stale by another snapshot.
+static int run_watch(kp_engine* e) {
+  kps_world* w = nullptr;
+  const uint32_t C = 130;
+  if (kps_create(6, 31, C, 0, 500, &w)) return 1;
+  uint64_t nc = 0, nb = 0;
+  const kp_cluster* cl = kps_clusters(w, &nc);
+  const kp_binding* bs = kps_bindings(w, &nb);
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  std::vector<uint8_t> mode(nb);
+  for (uint64_t i = 0; i < nb; i++) mode[i] = i % 11 == 3 ? KP_WATCH_SKIP : i % 11 == 7 ? KP_WATCH_ALWAYS : KP_WATCH_MATCH;
+  const std::vector<uint32_t> changed = {0, 129, 64, 64, 5};
+  std::vector<uint32_t> want;
+  for (uint64_t i = 0; i < nb; i++) {
+    const kp_binding& b = bs[i];
+    if (mode[i] == KP_WATCH_SKIP) continue;
+    const kp_cluster_affinity* a = nullptr;
+    if (b.n_cluster_affinities > 0) {
+      uint32_t t = 0;  // getAffinityIndex
+      for (uint32_t k = 0; k < b.n_cluster_affinities && b.observed_affinity_name.len; k++) {
+        const kp_str& nm = b.cluster_affinities[k].affinity_name;
+        if (nm.len == b.observed_affinity_name.len &&
+            std::string(nm.ptr, nm.len) == std::string(b.observed_affinity_name.ptr, nm.len)) {
+          t = k;
+          break;
+        }
+      }
+      a = &b.cluster_affinities[t].affinity;
+    } else if (b.has_cluster_affinity) {
+      a = &b.cluster_affinity;
+    }
+    bool listed = mode[i] == KP_WATCH_ALWAYS || !a;
+    for (uint32_t c : changed) listed = listed || kpo_cluster_matches(&cl[c], a);
+    if (listed) want.push_back((uint32_t)i);
+  }
+  kp_snapshot *s = nullptr, *s2 = nullptr;
+  kp_watch* wt = nullptr;
+  int bad = 0;
+  if (kp_snapshot_create(e, cl, nc, &o, &s) || kp_snapshot_create(e, cl, nc, &o, &s2) ||
+      kp_watch_create(e, s, bs, nb, mode.data(), &wt)) {
+    fprintf(stderr, "watch: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  }
+  for (int rows = 0; rows < 2 && !bad; rows++) {
+    if (rows) setenv("KP_PAIR_ROWS", "1", 1);
+    kp_affected got{};
+    if (kp_affected_bindings(e, wt, s, changed.data(), changed.size(), &got)) {
+      fprintf(stderr, "watch: engine error: %s\n", kp_last_error(e));
+      bad++;
+    } else if (std::vector<uint32_t>(got.bindings, got.bindings + got.n) != want) {
+      fprintf(stderr, "watch: rows=%d: %llu bindings listed, expected %llu\n", rows, (unsigned long long)got.n,
+              (unsigned long long)want.size());
+      bad++;
+    }
+    unsetenv("KP_PAIR_ROWS");
+  }
+  kp_affected none{};
+  if (!bad && kp_affected_bindings(e, wt, s2, changed.data(), changed.size(), &none) != KP_ESTATE) bad++;
+  if (wt) kp_watch_destroy(wt);
+  if (s2) kp_snapshot_destroy(s2);
+  if (s) kp_snapshot_destroy(s);
+  kps_destroy(w);
+  printf("watch: %llu bindings x %u clusters, %llu listed, %d mismatches\n", (unsigned long long)nb, C,
+         (unsigned long long)want.size(), bad);
+  return bad ? 1 : 0;
+}
+
 // `driver ceiling`: the snapshots at which a workgroup's LDS is full (tests/test_lds_ceiling.py:
 // 18 624 clusters without spread bindings, 14 336 with them, and the class-order switch at
 // 16 384 / 16 385) instead of the small universes, so the sanitizer sees every global array
@@ -625,6 +699,7 @@ int main(int argc, char** argv) {
   if (!ceiling) fails += run_affinity_answers(e);
   if (!ceiling) fails += run_batch_answers(e);
   if (!ceiling) fails += run_pack_stages(e);
+  if (!ceiling) fails += run_watch(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
