@@ -378,6 +378,50 @@ typedef struct kp_results_packed {
   const uint64_t* wide_offsets; /* n_bindings + 1, or NULL when n_wide == 0 */
 } kp_results_packed;
 
+/* The delta form of kp_results (kp_schedule_batch_delta): the targets of the bindings whose
+ * placement the call CHANGED, compared on the device with the spec.Clusters the binding was
+ * packed with. It is what patchScheduleResultForResourceBinding (pkg/scheduler/
+ * scheduler.go:686-718) needs: a patch for the changed bindings, nothing for the others.
+ * For binding b of the batch, after the call:
+ *   - status[b] != KP_STATUS_OK: b is never listed as changed. It has no targets in any
+ *     form; the caller acts on the status, which is returned for every binding.
+ *   - status[b] == KP_STATUS_OK: b is UNCHANGED exactly when its result equals spec.Clusters
+ *     as a multiset of (cluster, replicas) pairs, where spec.Clusters means all n_clusters
+ *     entries the caller passed: the comparison of helper.IsScheduleResultEqual
+ *     (test/helper/scheduler.go:26-40). So
+ *       . a spec.Clusters name the snapshot does not hold makes the binding changed;
+ *       . a repeated name makes it changed (a result never repeats a cluster, so lists of
+ *         equal size cannot match);
+ *       . an empty result against an empty spec.Clusters is unchanged;
+ *       . replicas compare as full int32: negative and wrapped values and the
+ *         zero-replica entries of enable_empty_workload_propagation included. No replicas
+ *         value serves as an "absent" sentinel.
+ * One deliberate difference from the reference: its merge patch compares the list in
+ * order, so a result that only reorders spec.Clusters is patched there and is reported
+ * unchanged here. The two states are equal under the reference's own result equality, and
+ * the engine's entry order is the reference's only where that is deterministic (kp_results).
+ *
+ * status, err_code and err_arg (n_bindings each) are byte for byte what kp_schedule_batch
+ * returns for the same batch. changed holds the n_changed changed bindings' batch indices,
+ * ascending; the targets of changed[i] are entries [offsets[i], offsets[i+1]) of
+ * cluster_idx / replicas, in the entry order and with the caller's cluster indices of
+ * kp_results. n_targets = offsets[n_changed]; n_targets_all = what kp_results.n_targets
+ * would have been. Nothing but the three status arrays is sized by n_bindings. Engine-owned,
+ * valid until the next call on the engine, as kp_results. */
+typedef struct kp_results_delta {
+  uint64_t n_bindings;
+  const int32_t* status;    /* n_bindings, as kp_results */
+  const int32_t* err_code;
+  const int64_t* err_arg;
+  uint64_t n_changed;
+  const uint32_t* changed;  /* n_changed batch indices, ascending */
+  const uint64_t* offsets;  /* n_changed + 1: CSR over the changed bindings only */
+  const uint32_t* cluster_idx;
+  const int32_t* replicas;
+  uint64_t n_targets;       /* targets of the changed bindings */
+  uint64_t n_targets_all;   /* what kp_results.n_targets would have been */
+} kp_results_delta;
+
 /* Results of kp_schedule_affinities, engine-owned like kp_results. `results` holds
  * each binding's final Schedule outcome: the first successful term's targets, or,
  * when every term failed, the FIRST term's error class/code/arg with no targets
@@ -682,6 +726,23 @@ int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* b, kp_results_packe
 /* Expands packed results into caller-provided arrays of in->n_targets entries each, the
  * cluster_idx / replicas of kp_results. Plain host code: no engine, no device. */
 int kp_results_unpack(const kp_results_packed* in, uint32_t* cluster_idx, int32_t* replicas);
+
+/* kp_schedule_batch with the results in the delta form (kp_results_delta): the same
+ * kernels, then each binding's result compared with its spec.Clusters on the device, and
+ * only the changed bindings' indices and targets copied back. Batches of every
+ * kp_batch_create* variant schedule in this form, their estimator and filter rows honoured
+ * (and the out-of-tree plugin gate applied) as by kp_schedule_batch.
+ * _submit_delta / _collect_delta are the two halves with the contract of the packed ones:
+ * one submitted call per batch across the three formats (KP_ESTATE on a second submit, or
+ * on a collect with nothing submitted; KP_EINVAL from either half while
+ * kp_engine_set_profile is on, a submitted call staying collectable for later), a submitted
+ * call is collected by its own format's function (another's returns KP_ESTATE and leaves
+ * the call collectable), and a batch may change format from call to call. A completed
+ * delta call is a completed schedule call for kp_fit_diagnosis_batch(bindings == NULL).
+ * kp_schedule_affinities* and kp_multi_* have no delta form. */
+int kp_schedule_batch_delta(kp_engine* e, kp_batch* b, kp_results_delta* out);
+int kp_schedule_batch_submit_delta(kp_engine* e, kp_batch* b);
+int kp_schedule_batch_collect_delta(kp_engine* e, kp_batch* b, kp_results_delta* out);
 
 /* Scheduler.scheduleResourceBindingWithClusterAffinities (scheduler.go:618-684),
  * batched: bindings with n_cluster_affinities > 0 start at getAffinityIndex of their

@@ -205,6 +205,16 @@ class kp_results_packed(C.Structure):
                 ("wide_replicas", C.POINTER(i32)), ("n_wide", u64), ("wide_offsets", C.POINTER(u64))]
 
 
+class kp_results_delta(C.Structure):
+    """kp_results for the bindings whose placement the call changed (kp_api.h): the status
+    arrays for every binding; changed[n_changed] batch indices, ascending, and a CSR of
+    their targets alone. n_targets_all = what kp_results.n_targets would have been."""
+    _fields_ = [("n_bindings", u64), ("status", C.POINTER(i32)), ("err_code", C.POINTER(i32)),
+                ("err_arg", C.POINTER(i64)), ("n_changed", u64), ("changed", C.POINTER(u32)),
+                ("offsets", C.POINTER(u64)), ("cluster_idx", C.POINTER(u32)), ("replicas", C.POINTER(i32)),
+                ("n_targets", u64), ("n_targets_all", u64)]
+
+
 class kp_binding_key(C.Structure):
     _fields_ = [("uid", kp_str), ("generation", i64)]
 

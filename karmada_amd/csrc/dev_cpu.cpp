@@ -447,6 +447,25 @@ int pack_wide(stream_t, const uint64_t* start, const uint64_t* offsets, const ui
   for (int b = 0; b < n; b++) body_pack_wide(CpuBlk{red}, b, start, offsets, wide_offsets, in_rep, out, n);
   return 0;
 }
+int changed(stream_t, const BatchView& bv, const int32_t* status, const uint64_t* start, const uint32_t* count,
+            const uint32_t* in_idx, const int32_t* in_rep, uint32_t* flag, uint32_t* mcount) {
+  return grid("k_changed", bv.B, 0, [&](int b, unsigned char*) {
+    body_changed(CpuBlk{nullptr}, b, bv.hdr, bv.ipool, status, start, count, in_idx, in_rep, flag, mcount);
+  });
+}
+int changed_long(stream_t, const SnapView& s, const BatchView& bv, const int32_t* list, int n, const int32_t* status,
+                 const uint64_t* start, const uint32_t* count, const uint32_t* in_idx, const int32_t* in_rep,
+                 uint32_t* flag, uint32_t* mcount) {
+  return grid("k_changed_long", n, changed_lds_bytes(s.Cp), [&](int i, unsigned char* sm) {
+    body_changed_long(CpuBlk{(int64_t*)sm}, list[i], sm, s.Cp, bv.hdr, bv.ipool, status, start, count, in_idx, in_rep,
+                      flag, mcount);
+  });
+}
+int changed_list(stream_t, int n, const uint32_t* flag, const uint64_t* chg_off, const uint64_t* moff,
+                 uint32_t* changed, uint64_t* out_off) {
+  for (int b = 0; b < n; b++) body_changed_list(b, n, flag, chg_off, moff, changed, out_off);
+  return 0;
+}
 
 }  // namespace dev
 }  // namespace kp

@@ -302,6 +302,53 @@ static int ensure_packed(kp_engine* e, kp_batch* bt) {
   return 0;
 }
 
+// The delta result form's buffers, allocated on the batch's first delta call (kp_host.h; a
+// batch never scheduled in this form allocates and uploads nothing for it). The list of
+// long-list bindings is made here from the host headers and uploaded on the call's stream.
+static int ensure_delta(kp_engine* e, kp_batch* bt) {
+  const size_t B = (size_t)std::max(1, bt->B);
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  if (!bt->dflag_d) {
+    std::vector<int32_t> longs;
+    for (int b = 0; b < bt->B; b++)
+      if (changed_long(bt->hdr[b])) longs.push_back(b);
+    if (!longs.empty() && changed_lds_bytes(bt->snap->Cp) > e->max_lds) {
+      e->err = "delta results: snapshot too large for one workgroup's LDS (" +
+               std::to_string(changed_lds_bytes(bt->snap->Cp)) + " > " + std::to_string(e->max_lds) + " bytes)";
+      return KP_ENOTSUP;
+    }
+    const size_t o_cnt = up(4 * B), o_chg = o_cnt + up(4 * B), o_off = o_chg + up(4 * B),
+                 o_moff = o_off + up(8 * (B + 1)), o_out = o_moff + up(8 * (B + 1)), o_long = o_out + up(8 * (B + 1));
+    void* p = nullptr;
+    if (dev::alloc(&p, o_long + 4 * std::max<size_t>(1, longs.size()))) {
+      e->err = std::string("delta results: ") + dev::last_error();
+      return KP_EDEVICE;
+    }
+    char* q = (char*)p;
+    if (!longs.empty() && (dev::h2d(q + o_long, longs.data(), 4 * longs.size(), e->stream) || dev::sync(e->stream))) {
+      e->err = std::string("delta results: ") + dev::last_error();
+      dev::release(p);
+      return KP_EDEVICE;
+    }
+    bt->dflag_d = (uint32_t*)q;
+    bt->dcount_d = (uint32_t*)(q + o_cnt);
+    bt->dchanged_d = (uint32_t*)(q + o_chg);
+    bt->dchg_off_d = (uint64_t*)(q + o_off);
+    bt->dmoff_d = (uint64_t*)(q + o_moff);
+    bt->dout_off_d = (uint64_t*)(q + o_out);
+    bt->dlong_d = (int32_t*)(q + o_long);
+    bt->n_dlong = (int)longs.size();
+  }
+  if (!bt->h_delta) {
+    bt->h_delta = (uint64_t*)pinned_get(32 + 8 * (B + 1) + 4 * B, &bt->h_delta_bytes);
+    if (!bt->h_delta) {
+      e->err = "delta results: page-locked buffers";
+      return KP_ENOMEM;
+    }
+  }
+  return KP_OK;
+}
+
 }  // extern "C"
 
 // Per-kernel profiling (kp_engine_set_profile): prof_begin records the start event of
@@ -413,15 +460,17 @@ static int refuse_out_of_tree(kp_engine* e, const kp_snapshot* s, uint32_t answe
 // next batch's kernels queued on the engine's stream while it collects the previous one.
 // packed: the results are gathered in the packed form (k_pack, the escape counts' scan,
 // k_pack_wide) instead of the CSR (k_compact), for schedule_finish to return as
-// kp_results_packed.
+// kp_results_packed. delta: k_changed compares every result with the binding's spec.Clusters,
+// and only the changed bindings' results are compacted and copied back (kp_results_delta).
 //
 // schedule_submit queues the call in six stages (submit_rows ... submit_results, in that
 // order) over the engine's three streams; SubmitCtx is what the stages share.
+enum ResultForm : int { RF_WIDE = 0, RF_PACKED, RF_DELTA };
 struct SubmitCtx {
   kp_engine* e;
   kp_batch* bt;
   kp_snapshot* s;
-  bool packed;
+  ResultForm form;
   KArgs ka;       // the batch's launch arguments: a launch copies them and sets its list
   SelectExtra sx;
   int kslot = 0;  // device argument slots taken so far (with_args)
@@ -447,7 +496,7 @@ struct SubmitCtx {
   double th0 = 0, th1 = 0;  // the region chain's host step
   static constexpr int cap = kSmallMax + kTgtSmallMax + 16;
 
-  SubmitCtx(kp_engine* e_, kp_batch* bt_, bool packed_) : e(e_), bt(bt_), s(bt_->snap), packed(packed_) {
+  SubmitCtx(kp_engine* e_, kp_batch* bt_, ResultForm form_) : e(e_), bt(bt_), s(bt_->snap), form(form_) {
     fast = kp_env_flag("KP_PAIR_GENERIC") || !bt->fast_ok ? EST_GENERIC : s->est_kind;
     bits = fast != EST_GENERIC && s->view.n_bits > 0 && !kp_env_flag("KP_PAIR_ROWS");
     ka.s = s->view;
@@ -941,6 +990,11 @@ static int submit_slow(SubmitCtx& c) {
 // target into cidx_d, the escape counts scanned into wide_offsets — the CSR scan's chunk
 // totals are consumed by now, one stream — and the escaped replicas into crep_d); the
 // per-binding arrays are read back here, the CSR by schedule_finish once it knows its size.
+// The delta form keeps the first scan for its total alone (n_targets_all), then k_changed /
+// k_changed_long write each binding's flag and masked count, both are scanned (off_part
+// again, as the packed form's second scan), k_compact gathers the changed bindings' results
+// over the masked offsets and k_changed_list writes their indices and offsets; of the
+// arrays sized by B only the three status arrays are read back.
 static int submit_results(SubmitCtx& c) {
   kp_engine* e = c.e;
   kp_batch* bt = c.bt;
@@ -951,7 +1005,25 @@ static int submit_results(SubmitCtx& c) {
   HIPCHK(dev::stream_wait(st, e->ev[EV_SLOW_END]));  // k_slow (stream3) and every select kernel precede the results
   HIPCHK(dev::event_record(e->ev[EV_SELECT_END], st));
   KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->count, B, bt->offsets_d, bt->off_part));
-  if (c.packed) {
+  if (c.form == RF_DELTA) {
+    KPROF(st, "k_changed", B, -1,
+          dev::changed(st, bt->view, bt->status, bt->start, bt->count, bt->out_idx, bt->out_rep, bt->dflag_d,
+                       bt->dcount_d));
+    if (bt->n_dlong)
+      KPROF(st, "k_changed_long", bt->n_dlong, -1,
+            dev::changed_long(st, s->view, bt->view, bt->dlong_d, bt->n_dlong, bt->status, bt->start, bt->count,
+                              bt->out_idx, bt->out_rep, bt->dflag_d, bt->dcount_d));
+    HIPCHK(dev::d2h(bt->h_delta + 2, bt->offsets_d + B, 8, st));  // n_targets_all, before off_part is reused
+    KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->dcount_d, B, bt->dmoff_d, bt->off_part));
+    KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->dflag_d, B, bt->dchg_off_d, bt->off_part));
+    KPROF(st, "k_compact", B, -1,
+          dev::compact(st, bt->start, bt->dcount_d, bt->dmoff_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->crep_d, B,
+                       s->view.perm));
+    KPROF(st, "k_changed_list", B, -1,
+          dev::changed_list(st, B, bt->dflag_d, bt->dchg_off_d, bt->dmoff_d, bt->dchanged_d, bt->dout_off_d));
+    HIPCHK(dev::d2h(bt->h_delta, bt->dchg_off_d + B, 8, st));
+    HIPCHK(dev::d2h(bt->h_delta + 1, bt->dmoff_d + B, 8, st));
+  } else if (c.form == RF_PACKED) {
     KPROF(st, "k_pack", B, -1,
           dev::pack(st, bt->start, bt->offsets_d, bt->out_idx, bt->out_rep, bt->cidx_d, bt->wcount_d, B, s->view.perm));
     KPROF(st, "k_offsets", B, -1, dev::offsets(st, bt->status, bt->wcount_d, B, bt->woff_d, bt->off_part));
@@ -966,11 +1038,11 @@ static int submit_results(SubmitCtx& c) {
   bt->h_status.resize(B);
   bt->h_err.resize(B);
   bt->h_arg.resize(B);
-  bt->h_offsets.resize(B + 1);
+  if (c.form != RF_DELTA) bt->h_offsets.resize(B + 1);
   HIPCHK(dev::d2h(bt->h_status.data(), bt->status, 4 * (size_t)B, st));
   HIPCHK(dev::d2h(bt->h_err.data(), bt->errc, 4 * (size_t)B, st));
   HIPCHK(dev::d2h(bt->h_arg.data(), bt->arg, 8 * (size_t)B, st));
-  HIPCHK(dev::d2h(bt->h_offsets.data(), bt->offsets_d, 8 * (size_t)(B + 1), st));
+  if (c.form != RF_DELTA) HIPCHK(dev::d2h(bt->h_offsets.data(), bt->offsets_d, 8 * (size_t)(B + 1), st));
   HIPCHK(dev::d2h(bt->h_stats, bt->stats, sizeof(bt->h_stats), st));
   SchedPend& pd = bt->pend;
   if (!pd.ev && dev::event_create(&pd.ev)) {
@@ -982,7 +1054,8 @@ static int submit_results(SubmitCtx& c) {
   return KP_OK;
 }
 
-static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
+static int schedule_submit(kp_engine* e, kp_batch* bt, ResultForm form) {
+  const bool packed = form == RF_PACKED;
   if (!e || !bt) return KP_EINVAL;
   if (int rc = refuse_out_of_tree(e, bt->snap, bt->flt_plugins)) return rc;
   (void)dev::set_device(e->device);
@@ -992,6 +1065,8 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
     return KP_ENOTSUP;
   }
   if (packed && ensure_packed(e, bt)) return KP_EDEVICE;
+  if (form == RF_DELTA)
+    if (int rc = ensure_delta(e, bt)) return rc;
   SchedPend& pd = bt->pend;
   {
     const dev::event_t ev = pd.ev;  // (the event is kept across calls)
@@ -1000,6 +1075,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
   }
   bt->sched_done = false;
   pd.packed = packed;
+  pd.delta = form == RF_DELTA;
   pd.t0 = now_ms();
   pd.seq = ++e->submit_seq;
   if (bt->B == 0) {
@@ -1022,7 +1098,7 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
 #endif
   HIPCHK(dev::event_record(e->ev[EV_FILLS], st));
   HIPCHK(dev::stream_wait(e->stream2, e->ev[EV_FILLS]));  // the fills above precede every kernel
-  SubmitCtx c(e, bt, packed);
+  SubmitCtx c(e, bt, form);
   if (!c.bits) {
     if (ensure_rows(e, bt)) return KP_EDEVICE;
     c.ka.est = bt->est;
@@ -1046,19 +1122,23 @@ static int schedule_submit(kp_engine* e, kp_batch* bt, bool packed) {
   return KP_OK;
 }
 
-// Exactly one of out / pout is given: the format the caller collects in, which must be
-// the one the call was submitted in.
-static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout) {
-  if (!e || !bt || (!out && !pout)) return KP_EINVAL;
+// Exactly one of out / pout / dout is given: the format the caller collects in, which must
+// be the one the call was submitted in.
+static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout,
+                           kp_results_delta* dout = nullptr) {
+  if (!e || !bt || (!out && !pout && !dout)) return KP_EINVAL;
   SchedPend& pd = bt->pend;
   if (!pd.live) {
     e->err = "kp_schedule_batch_collect: the batch has no submitted call";
     return KP_ESTATE;
   }
-  const bool packed = pout != nullptr;
-  if (pd.packed != packed) {  // (the call stays submitted, for the right function to collect)
-    e->err = pd.packed ? "kp_schedule_batch_collect: the submitted call is packed (kp_schedule_batch_collect_packed)"
-                       : "kp_schedule_batch_collect_packed: the submitted call is not packed (kp_schedule_batch_collect)";
+  const bool packed = pout != nullptr, delta = dout != nullptr;
+  if (pd.packed != packed || pd.delta != delta) {  // (the call stays submitted, for the right function to collect)
+    static const char* const fn[3] = {"kp_schedule_batch_collect", "kp_schedule_batch_collect_packed",
+                                      "kp_schedule_batch_collect_delta"};
+    static const char* const is[3] = {"wide", "packed", "delta"};
+    const int sub = pd.delta ? 2 : pd.packed ? 1 : 0;
+    e->err = std::string(fn[delta ? 2 : packed ? 1 : 0]) + ": the submitted call is " + is[sub] + " (" + fn[sub] + ")";
     return KP_ESTATE;
   }
   pd.live = false;
@@ -1070,7 +1150,12 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     bt->h_status.clear();
     bt->sched_done = true;
     auto none = [&](auto* r) { memset(r, 0, sizeof(*r)), r->offsets = bt->h_offsets.data(); };
-    packed ? none(pout) : none(out);
+    if (delta) {
+      memset(dout, 0, sizeof(*dout));
+      dout->offsets = bt->h_offsets.data();
+    } else {
+      packed ? none(pout) : none(out);
+    }
     return KP_OK;
   }
   dev::stream_t st = e->stream;
@@ -1085,7 +1170,8 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     HIPCHK(dev::sync(st));
   }
   double tc0 = now_ms();
-  const uint64_t tot = bt->h_offsets[B];
+  // (a delta call: the CSR of the changed bindings alone, h_delta[1] entries)
+  const uint64_t tot = delta ? bt->h_delta[1] : bt->h_offsets[B];
   if (tot > bt->h_res_cap || !bt->h_cidx) {
     buf_pool().put(-1, bt->h_cidx, bt->h_cidx_bytes);
     buf_pool().put(-1, bt->h_crep, bt->h_crep_bytes);
@@ -1104,7 +1190,16 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   // (a packed call: tot packed words in cidx_d and the n_wide <= tot escaped replicas in
   // crep_d, 4 * (tot + n_wide) bytes instead of 8 * tot)
   uint64_t n_wide = packed ? bt->h_woff[B] : 0;
-  if (packed) {
+  uint64_t n_changed = delta ? bt->h_delta[0] : 0, n_all = delta ? bt->h_delta[2] : 0;
+  uint64_t* const d_off = bt->h_delta ? bt->h_delta + 4 : nullptr;
+  uint32_t* const d_chg = bt->h_delta ? (uint32_t*)(bt->h_delta + 4 + (size_t)std::max(1, B) + 1) : nullptr;
+  if (delta) {
+    HIPCHK(dev::d2h(d_off, bt->dout_off_d, 8 * (n_changed + 1), st));
+    HIPCHK(dev::d2h(d_chg, bt->dchanged_d, 4 * n_changed, st));
+    if (tot) HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * tot, st));
+    if (tot) HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * tot, st));
+    HIPCHK(dev::sync(st));
+  } else if (packed) {
     if (tot) HIPCHK(dev::d2h(bt->h_cidx, bt->cidx_d, 4 * tot, st));
     if (n_wide) HIPCHK(dev::d2h(bt->h_crep, bt->crep_d, 4 * n_wide, st));
     if (tot) HIPCHK(dev::sync(st));
@@ -1126,7 +1221,31 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
         bt->h_arg[b] = (int64_t)s->perm[sets_ovf[j] - 1];
       }
   }
-  if (std::any_of(sets_ovf.begin(), sets_ovf.end(), [](uint32_t v) { return v != 0; })) {
+  const bool any_ovf = std::any_of(sets_ovf.begin(), sets_ovf.end(), [](uint32_t v) { return v != 0; });
+  if (any_ovf && delta) {
+    // (the failed bindings leave the changed list, and n_targets_all loses their targets,
+    // changed or not: the one case that reads the batch's full offsets back)
+    bt->h_offsets.resize(B + 1);
+    HIPCHK(dev::d2h(bt->h_offsets.data(), bt->offsets_d, 8 * (size_t)(B + 1), st));
+    HIPCHK(dev::sync(st));
+    for (int32_t b : bt->l_sets)
+      if (bt->h_err[b] == KP_ERR_SETS_CAPACITY && bt->h_status[b] == KP_STATUS_ERROR)
+        n_all -= bt->h_offsets[b + 1] - bt->h_offsets[b];
+    uint64_t w = 0, nc = 0;
+    for (uint64_t i = 0; i < n_changed; i++) {
+      const uint64_t lo = d_off[i], hi = d_off[i + 1];
+      const uint32_t b = d_chg[i];
+      if (bt->h_status[b] != KP_STATUS_OK) continue;
+      d_chg[nc] = b;
+      d_off[nc++] = w;
+      for (uint64_t k = lo; k < hi; k++, w++) {
+        bt->h_cidx[w] = bt->h_cidx[k];
+        bt->h_crep[w] = bt->h_crep[k];
+      }
+    }
+    d_off[nc] = w;
+    n_changed = nc;
+  } else if (any_ovf) {
     uint64_t w = 0, ww = 0;  // (packed: h_cidx holds the words, h_crep the escaped replicas)
     for (int b = 0; b < B; b++) {
       const uint64_t lo = bt->h_offsets[b], hi = bt->h_offsets[b + 1];
@@ -1148,7 +1267,7 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     bt->h_offsets[B] = w;
     if (packed) bt->h_woff[B] = n_wide = ww;
   }
-  const uint64_t tot_out = bt->h_offsets[B];
+  const uint64_t tot_out = delta ? d_off[n_changed] : bt->h_offsets[B];
   double t1 = now_ms();
   if (e->prof) prof_fold(e, bt->h_stats);
   // pair: the pair launch, or k_est_class + k_filter (stream2; filter: k_filter
@@ -1216,7 +1335,19 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
     r->offsets = bt->h_offsets.data();
     r->n_targets = tot_out;
   };
-  if (packed) {
+  if (delta) {
+    dout->n_bindings = (uint64_t)B;
+    dout->status = bt->h_status.data();
+    dout->err_code = bt->h_err.data();
+    dout->err_arg = bt->h_arg.data();
+    dout->n_changed = n_changed;
+    dout->changed = d_chg;
+    dout->offsets = d_off;
+    dout->cluster_idx = bt->h_cidx;
+    dout->replicas = bt->h_crep;
+    dout->n_targets = tot_out;
+    dout->n_targets_all = n_all;
+  } else if (packed) {
     common(pout);
     pout->targets = bt->h_cidx;
     pout->wide_replicas = bt->h_crep;
@@ -1230,15 +1361,16 @@ static int schedule_finish(kp_engine* e, kp_batch* bt, kp_results* out, kp_resul
   return KP_OK;
 }
 
-// The wide and the packed entry points share one body per call. The one-shot call: exactly
-// one of out / pout is given, as for schedule_finish.
-static int schedule_both(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout) {
-  if (!out && !pout) return KP_EINVAL;
-  if (int rc = schedule_submit(e, bt, pout != nullptr)) return rc;
-  return schedule_finish(e, bt, out, pout);
+// The wide, the packed and the delta entry points share one body per call. The one-shot
+// call: exactly one of out / pout / dout is given, as for schedule_finish.
+static int schedule_both(kp_engine* e, kp_batch* bt, kp_results* out, kp_results_packed* pout,
+                         kp_results_delta* dout = nullptr) {
+  if (!out && !pout && !dout) return KP_EINVAL;
+  if (int rc = schedule_submit(e, bt, dout ? RF_DELTA : pout ? RF_PACKED : RF_WIDE)) return rc;
+  return schedule_finish(e, bt, out, pout, dout);
 }
 // The submit call; `who` names the entry point in the error texts.
-static int submit_call(kp_engine* e, kp_batch* bt, bool packed, const char* who) {
+static int submit_call(kp_engine* e, kp_batch* bt, ResultForm form, const char* who) {
   if (e && e->prof) {
     e->err = std::string(who) + ": per-kernel profiling covers kp_schedule_batch only";
     return KP_EINVAL;
@@ -1248,11 +1380,11 @@ static int submit_call(kp_engine* e, kp_batch* bt, bool packed, const char* who)
     e->err = std::string(who) + ": the batch's previous call is not collected";
     return KP_ESTATE;
   }
-  return batch_fence(e, bt, schedule_submit(e, bt, packed));
+  return batch_fence(e, bt, schedule_submit(e, bt, form));
 }
 int kp_schedule_batch(kp_engine* e, kp_batch* bt, kp_results* out) { return batch_fence(e, bt, schedule_both(e, bt, out, nullptr)); }
 int kp_schedule_batch_submit(kp_engine* e, kp_batch* bt) {
-  return submit_call(e, bt, false, "kp_schedule_batch_submit");
+  return submit_call(e, bt, RF_WIDE, "kp_schedule_batch_submit");
 }
 int kp_schedule_batch_collect(kp_engine* e, kp_batch* bt, kp_results* out) {
   return batch_fence(e, bt, schedule_finish(e, bt, out, nullptr));
@@ -1262,10 +1394,24 @@ int kp_schedule_batch_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out)
   return batch_fence(e, bt, schedule_both(e, bt, nullptr, out));
 }
 int kp_schedule_batch_submit_packed(kp_engine* e, kp_batch* bt) {
-  return submit_call(e, bt, true, "kp_schedule_batch_submit_packed");
+  return submit_call(e, bt, RF_PACKED, "kp_schedule_batch_submit_packed");
 }
 int kp_schedule_batch_collect_packed(kp_engine* e, kp_batch* bt, kp_results_packed* out) {
   return batch_fence(e, bt, schedule_finish(e, bt, nullptr, out));
+}
+// The delta result form (kp_results_delta): the same calls with the changed bindings alone.
+int kp_schedule_batch_delta(kp_engine* e, kp_batch* bt, kp_results_delta* out) {
+  return batch_fence(e, bt, schedule_both(e, bt, nullptr, nullptr, out));
+}
+int kp_schedule_batch_submit_delta(kp_engine* e, kp_batch* bt) {
+  return submit_call(e, bt, RF_DELTA, "kp_schedule_batch_submit_delta");
+}
+int kp_schedule_batch_collect_delta(kp_engine* e, kp_batch* bt, kp_results_delta* out) {
+  if (e && e->prof) {  // (a call submitted before profiling was turned on stays collectable after it is off)
+    e->err = "kp_schedule_batch_collect_delta: per-kernel profiling covers the one-call forms only";
+    return KP_EINVAL;
+  }
+  return batch_fence(e, bt, schedule_finish(e, bt, nullptr, nullptr, out));
 }
 int kp_results_unpack(const kp_results_packed* in, uint32_t* cluster_idx, int32_t* replicas) {
   if (!in || (in->n_targets && (!in->targets || !cluster_idx || !replicas))) return KP_EINVAL;

@@ -674,6 +674,50 @@ extern "C" __global__ void __launch_bounds__(64) k_pack_wide(const uint64_t* sta
 #else
 ;
 #endif
+// The delta result form: k_changed before the scans, one wave64 per binding, kChangedWaves
+// per workgroup and no LDS (the binding index through a scalar register, as k_filter);
+// k_changed_long, one workgroup per binding of the batch's long-list bindings, with the
+// rank-indexed table in LDS; k_changed_list, one thread per binding, after the scans.
+constexpr int kChangedWaves = 4;
+extern "C" __global__ void __launch_bounds__(64 * kChangedWaves) k_changed(int n, const BindHdr* hdr,
+                                                                         const int32_t* ipool, const int32_t* status,
+                                                                         const uint64_t* start, const uint32_t* count,
+                                                                         const uint32_t* in_idx, const int32_t* in_rep,
+                                                                         uint32_t* flag, uint32_t* mcount)
+#if KP_K(8)
+{
+  const int b = (int)(blockIdx.x * kChangedWaves) + kp_uniform((int)(threadIdx.x >> 6));
+  if (b >= n) return;  // wave-uniform
+  body_changed(WaveBlk{nullptr}, b, hdr, ipool, status, start, count, in_idx, in_rep, flag, mcount);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(kBlock) k_changed_long(const int32_t* list, int Cp, const BindHdr* hdr,
+                                                                    const int32_t* ipool, const int32_t* status,
+                                                                    const uint64_t* start, const uint32_t* count,
+                                                                    const uint32_t* in_idx, const int32_t* in_rep,
+                                                                    uint32_t* flag, uint32_t* mcount)
+#if KP_K(8)
+{
+  KP_SMEM;
+  body_changed_long(GpuBlk{(int64_t*)smem}, list[blockIdx.x], smem, Cp, hdr, ipool, status, start, count, in_idx, in_rep,
+                    flag, mcount);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(256) k_changed_list(int n, const uint32_t* flag, const uint64_t* chg_off,
+                                                                 const uint64_t* moff, uint32_t* changed,
+                                                                 uint64_t* out_off)
+#if KP_K(8)
+{
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b < n) body_changed_list(b, n, flag, chg_off, moff, changed, out_off);
+}
+#else
+;
+#endif
 
 // ---------------------------------------------------------------------------
 // Device interface (HIP)
@@ -1133,6 +1177,32 @@ int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const
               const int32_t* in_rep, int32_t* out, int n) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_pack_wide, dim3(n), dim3(64), 0, (hipStream_t)st, start, offsets, wide_offsets, in_rep, out, n);
+  return chk(hipGetLastError());
+}
+int changed(stream_t st, const BatchView& bv, const int32_t* status, const uint64_t* start, const uint32_t* count,
+            const uint32_t* in_idx, const int32_t* in_rep, uint32_t* flag, uint32_t* mcount) {
+  if (bv.B <= 0) return 0;
+  hipLaunchKernelGGL(k_changed, dim3((bv.B + kChangedWaves - 1) / kChangedWaves), dim3(64 * kChangedWaves), 0,
+                     (hipStream_t)st, bv.B, bv.hdr, bv.ipool, status, start, count, in_idx, in_rep, flag, mcount);
+  return chk(hipGetLastError());
+}
+int changed_long(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* list, int n, const int32_t* status,
+                 const uint64_t* start, const uint32_t* count, const uint32_t* in_idx, const int32_t* in_rep,
+                 uint32_t* flag, uint32_t* mcount) {
+  if (n <= 0) return 0;
+  const size_t smem = changed_lds_bytes(s.Cp);
+  if (smem > 65536 &&
+      chk(hipFuncSetAttribute((const void*)k_changed_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)))
+    return -1;
+  hipLaunchKernelGGL(k_changed_long, dim3(n), dim3(kBlock), smem, (hipStream_t)st, list, s.Cp, bv.hdr, bv.ipool, status,
+                     start, count, in_idx, in_rep, flag, mcount);
+  return chk(hipGetLastError());
+}
+int changed_list(stream_t st, int n, const uint32_t* flag, const uint64_t* chg_off, const uint64_t* moff,
+                 uint32_t* changed, uint64_t* out_off) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_changed_list, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)st, n, flag, chg_off, moff,
+                     changed, out_off);
   return chk(hipGetLastError());
 }
 

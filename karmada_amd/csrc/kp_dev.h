@@ -180,6 +180,19 @@ int pack(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint
          uint32_t* out, uint32_t* wide_count, int n, const uint32_t* perm);
 int pack_wide(stream_t st, const uint64_t* start, const uint64_t* offsets, const uint64_t* wide_offsets,
               const int32_t* in_rep, int32_t* out, int n);
+// The delta result form (kp_results_delta), before the scans: flag[b] = 1 and mcount[b] =
+// count[b] for a binding whose result differs from its spec.Clusters, 0 and 0 otherwise
+// (body_changed over every binding; body_changed_long over list[0, n), the bindings whose
+// header satisfies kp::changed_long, which body_changed leaves to it). changed_list, after
+// the scans of flag (chg_off) and mcount (moff), both [n + 1]: the changed bindings'
+// indices, ascending, and out_off[0 .. n_changed] = their CSR offsets.
+int changed(stream_t st, const BatchView& bv, const int32_t* status, const uint64_t* start, const uint32_t* count,
+            const uint32_t* in_idx, const int32_t* in_rep, uint32_t* flag, uint32_t* mcount);
+int changed_long(stream_t st, const SnapView& s, const BatchView& bv, const int32_t* list, int n, const int32_t* status,
+                 const uint64_t* start, const uint32_t* count, const uint32_t* in_idx, const int32_t* in_rep,
+                 uint32_t* flag, uint32_t* mcount);
+int changed_list(stream_t st, int n, const uint32_t* flag, const uint64_t* chg_off, const uint64_t* moff,
+                 uint32_t* changed, uint64_t* out_off);
 
 }  // namespace dev
 }  // namespace kp

@@ -472,6 +472,7 @@ struct kp_snapshot {
 struct SchedPend {
   bool live = false, empty = false, bits = false, top = false, spread_orders = false;
   bool packed = false;  // the call returns kp_results_packed (kp_schedule_batch_submit_packed)
+  bool delta = false;   // the call returns kp_results_delta (kp_schedule_batch_submit_delta)
   int fast = 0;
   double t0 = 0, th0 = 0, th1 = 0;
   uint64_t seq = 0;
@@ -604,6 +605,19 @@ struct kp_batch {
   uint64_t* woff_d = nullptr;
   uint64_t* h_woff = nullptr;
   size_t h_woff_bytes = 0;
+  // The delta result form (kp_results_delta), allocated on the batch's first delta call
+  // (ensure_delta), one device allocation behind dflag_d: per-binding flags and masked
+  // counts [B], their scans [B + 1] each, the changed list [B], its CSR offsets [B + 1] and
+  // the batch's long-list bindings (kp::changed_long, n_dlong of them). h_delta, page-locked:
+  // [n_changed, n_targets, n_targets_all, pad | offsets [B + 1] | changed [B]], of which a
+  // call copies the totals, n_changed + 1 offsets and n_changed indices. The delta CSR takes
+  // cidx_d / crep_d and h_cidx / h_crep, as the wide one does.
+  uint32_t *dflag_d = nullptr, *dcount_d = nullptr, *dchanged_d = nullptr;
+  uint64_t *dchg_off_d = nullptr, *dmoff_d = nullptr, *dout_off_d = nullptr;
+  int32_t* dlong_d = nullptr;
+  int n_dlong = 0;
+  uint64_t* h_delta = nullptr;
+  size_t h_delta_bytes = 0;
   // The batch's device arena and page-locked buffers go back to the process-wide
   // pools on destruction, where another batch (of any engine) may take them at
   // once. An entry point that fails part-way leaves kernels queued that still
@@ -636,7 +650,9 @@ struct kp_batch {
     buf_pool().put(-1, h_crep, h_crep_bytes);
     buf_pool().put(-1, h_kargs, h_kargs_bytes);
     buf_pool().put(-1, h_woff, h_woff_bytes);
+    buf_pool().put(-1, h_delta, h_delta_bytes);
     if (est) dev::release(est);
+    if (dflag_d) dev::release(dflag_d);  // (one allocation)
     if (wcount_d) dev::release(wcount_d);  // (one allocation: woff_d lies behind the counts)
   }
   std::vector<RegionOut> h_rout;

@@ -2219,4 +2219,116 @@ KP_FI void body_pack_wide(const BLK& B, int blk, const uint64_t* start, const ui
   }
 }
 
+// The delta result form (kp_results_delta): binding b is unchanged when its status is OK and
+// its result equals spec.Clusters (all n_targets_all entries) as a multiset of (cluster,
+// replicas) pairs; a binding of any other status is never listed. flag[b] = 1 for a changed
+// binding, mcount[b] = its count (0 otherwise): the masked counts' scan is the delta CSR.
+// A name the snapshot does not hold (n_targets_all != tgt_cnt), a repeated name
+// (BF_DUP_TARGETS: a result never repeats a cluster) or another size decide at once. With
+// the sizes equal and no previous name repeated, the multisets are equal iff every previous
+// pair is found in the result, replicas compared as full int32 (no value stands for "absent").
+//
+// body_changed, one wave per binding: previous lists of up to kChangedWave entries, lane j
+// holding previous pair j and the result's pairs read lane by lane (registers only). A longer
+// previous list that passes the size checks is body_changed_long's (changed_long: the batch's
+// list of them is made on the host from the same header fields).
+constexpr int kChangedWave = 64;
+KP_HD inline bool changed_long(const BindHdr& h) {
+  return h.tgt_cnt > kChangedWave && h.n_targets_all == h.tgt_cnt && !(h.flags & BF_DUP_TARGETS);
+}
+template <class BLK>
+KP_FI void body_changed(const BLK& B, int b, const BindHdr* hdr, const int32_t* ipool, const int32_t* status,
+                        const uint64_t* start, const uint32_t* count, const uint32_t* in_idx, const int32_t* in_rep,
+                        uint32_t* flag, uint32_t* mcount) {
+  const BindHdr& h = hdr[b];
+  const int T = h.tgt_cnt;
+  uint32_t c = 0;
+  bool ch = false;
+  if (status[b] == KP_STATUS_OK) {
+    c = count[b];
+    if (h.n_targets_all != T || (h.flags & BF_DUP_TARGETS) || c != (uint32_t)T) {
+      ch = true;
+    } else if (T > kChangedWave) {
+      return;  // wave-uniform: body_changed_long writes this binding's pair
+    } else if (T > 0) {
+      const int ww = B.wwidth(), lane = B.lane() & (ww - 1);
+      const uint64_t s = start[b];
+      bool miss = false;
+      for (int jb = 0; jb < T; jb += ww) {  // (one trip on the device; the host build's wave is one lane)
+        const int j = jb + lane;
+        const uint32_t pr = j < T ? (uint32_t)ipool[h.tgt_off + 2 * j] : 0u;
+        const int32_t pv = j < T ? ipool[h.tgt_off + 2 * j + 1] : 0;
+        bool found = false;
+        for (int kb = 0; kb < T; kb += ww) {
+          const int k = kb + lane;
+          const uint32_t rr = k < T ? in_idx[s + k] : 0u;
+          const int32_t rv = k < T ? in_rep[s + k] : 0;
+          const int nq = T - kb < ww ? T - kb : ww;
+          for (int q = 0; q < nq; q++) found |= (B.wread(rr, q) == pr) & (B.wread(rv, q) == pv);
+        }
+        miss |= j < T && !found;
+      }
+      ch = B.wballot(miss) != 0;
+    }
+  }
+  if (B.lane() == 0) {
+    flag[b] = ch ? 1u : 0u;
+    mcount[b] = ch ? c : 0u;
+  }
+}
+
+// A long previous list (changed_long), one workgroup per binding: the result goes into a
+// rank-indexed table of replicas with a presence bit per cluster in LDS (changed_lds_bytes:
+// [red | tab[Cp] | bits]), and every previous pair is looked up in it: linear in the list,
+// which for a Duplicated binding is the whole fleet. A rank outside the table counts as a
+// difference instead of an LDS access.
+template <class BLK>
+KP_FI void body_changed_long(const BLK& B, int b, unsigned char* smem, int Cp, const BindHdr* hdr, const int32_t* ipool,
+                             const int32_t* status, const uint64_t* start, const uint32_t* count,
+                             const uint32_t* in_idx, const int32_t* in_rep, uint32_t* flag, uint32_t* mcount) {
+  const BindHdr& h = hdr[b];
+  const int T = h.tgt_cnt;
+  if (status[b] != KP_STATUS_OK) return;  // block-uniform: body_changed wrote these
+  const uint32_t c = count[b];
+  if (!changed_long(h) || c != (uint32_t)T) return;
+  int32_t* tab = (int32_t*)(smem + kRedBytes);
+  uint32_t* bits = (uint32_t*)(tab + Cp);
+  const int words = (Cp + 31) >> 5;
+  const uint64_t s = start[b];
+  for (int i = B.tid(); i < words; i += B.nth()) bits[i] = 0;
+  B.sync();
+  bool bad = false;
+  for (uint32_t i = (uint32_t)B.tid(); i < c; i += (uint32_t)B.nth()) {
+    const uint32_t r = in_idx[s + i];
+    if (r >= (uint32_t)Cp) {
+      bad = true;
+      continue;
+    }
+    tab[r] = in_rep[s + i];
+    kp_atomic_or(&bits[r >> 5], 1u << (r & 31));
+  }
+  B.sync();
+  for (int j = B.tid(); j < T; j += B.nth()) {
+    const uint32_t pr = (uint32_t)ipool[h.tgt_off + 2 * j];
+    const int32_t pv = ipool[h.tgt_off + 2 * j + 1];
+    if (pr >= (uint32_t)Cp || !((bits[pr >> 5] >> (pr & 31)) & 1u) || tab[pr] != pv) bad = true;
+  }
+  const bool ch = B.any(bad);
+  if (B.tid() == 0) {
+    flag[b] = ch ? 1u : 0u;
+    mcount[b] = ch ? c : 0u;
+  }
+}
+
+// The changed list and its CSR offsets, one thread per binding: chg_off = the scan of the
+// flags (ascending binding order), moff = the scan of the masked counts.
+KP_HD inline void body_changed_list(int b, int n, const uint32_t* flag, const uint64_t* chg_off, const uint64_t* moff,
+                                    uint32_t* changed, uint64_t* out_off) {
+  if (flag[b]) {
+    changed[chg_off[b]] = (uint32_t)b;
+    out_off[chg_off[b]] = moff[b];
+  }
+  if (b == n - 1) out_off[chg_off[n]] = moff[n];
+}
+
 }  // namespace kp

@@ -175,6 +175,9 @@ KP_HD inline size_t class_order_lds_bytes(int P) { return kRedBytes + 8 * (size_
 // k_fit_hist (body_fit_hist): per wave, the histogram bin of each distinct taint list.
 constexpr int kFitHistWaves = 4;  // one wave per diagnosed binding, as k_filter
 KP_HD inline size_t fit_hist_lds_bytes() { return 4 * (size_t)kTsetRowsMax; }
+// k_changed_long (body_changed_long): the result's replicas by cluster rank and a presence
+// bit per cluster (77 848 bytes at the 18 624-cluster ceiling).
+KP_HD inline size_t changed_lds_bytes(int Cp) { return kRedBytes + 4 * (size_t)Cp + 4 * (size_t)((Cp + 31) >> 5); }
 // k_slow (body_slow): target bits, lds_area bytes for the small serial problems, lds_sort
 // for the candidate sorts.
 KP_HD inline size_t slow_lds_bytes(int Cp, int lds_area, int lds_sort) {

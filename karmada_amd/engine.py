@@ -40,6 +40,7 @@ EXPORTS = (
     "kp_pack_cache_get_stats",
     "kp_schedule_batch", "kp_schedule_batch_submit", "kp_schedule_batch_collect",
     "kp_schedule_batch_packed", "kp_schedule_batch_submit_packed", "kp_schedule_batch_collect_packed", "kp_results_unpack",
+    "kp_schedule_batch_delta", "kp_schedule_batch_submit_delta", "kp_schedule_batch_collect_delta",
     "kp_schedule_affinities", "kp_schedule_affinities_ex", "kp_filter_batch", "kp_filter_reasons", "kp_fit_diagnosis_batch", "kp_score_batch", "kp_max_available_replicas", "kp_max_available_component_sets",
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
@@ -94,6 +95,9 @@ def load_library(path: str = LIB_PATH):
     L.kp_schedule_batch_submit_packed.argtypes = [vp, vp]
     L.kp_schedule_batch_collect_packed.argtypes = [vp, vp, C.POINTER(api.kp_results_packed)]
     L.kp_results_unpack.argtypes = [C.POINTER(api.kp_results_packed), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.kp_schedule_batch_delta.argtypes = [vp, vp, C.POINTER(api.kp_results_delta)]
+    L.kp_schedule_batch_submit_delta.argtypes = [vp, vp]
+    L.kp_schedule_batch_collect_delta.argtypes = [vp, vp, C.POINTER(api.kp_results_delta)]
     L.kp_schedule_affinities.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64,
                                          C.POINTER(api.kp_affinity_results)]
     L.kp_schedule_affinities_ex.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.c_uint64,
@@ -471,6 +475,39 @@ class Batch:
             raise EngineError("kp_results_unpack: the packed results are inconsistent")
         return ci, rep
 
+    def schedule_delta_raw(self) -> api.kp_results_delta:
+        """kp_schedule_batch_delta: every binding's status, and the targets of the bindings whose
+        placement differs from the spec.Clusters they were packed with (api.kp_results_delta)."""
+        r = api.kp_results_delta()
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_delta(eng.h, self.h, C.byref(r)), "kp_schedule_batch_delta")
+        return r
+
+    def submit_delta(self):
+        """kp_schedule_batch_submit_delta: submit() for a call collected by collect_delta()."""
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_submit_delta(eng.h, self.h), "kp_schedule_batch_submit_delta")
+
+    def collect_delta(self) -> api.kp_results_delta:
+        """kp_schedule_batch_collect_delta: the results of the call submit_delta() queued."""
+        r = api.kp_results_delta()
+        eng = self.snap.engine
+        eng._check(eng.L.kp_schedule_batch_collect_delta(eng.h, self.h, C.byref(r)),
+                   "kp_schedule_batch_collect_delta")
+        return r
+
+    def schedule_delta(self):
+        """(statuses, {index: result dict}): (status, err, arg) of every binding, and the
+        api.results_to_python dict of each binding whose placement changed."""
+        r = self.schedule_delta_raw()
+        st = [(int(r.status[i]), int(r.err_code[i]), int(r.err_arg[i])) for i in range(r.n_bindings)]
+        out = {}
+        for i in range(r.n_changed):
+            b = int(r.changed[i])
+            tg = sorted((int(r.cluster_idx[k]), int(r.replicas[k])) for k in range(r.offsets[i], r.offsets[i + 1]))
+            out[b] = {"status": st[b][0], "err": st[b][1], "arg": st[b][2], "targets": tg}
+        return st, out
+
     def fit_diagnosis_raw(self, bindings: Optional[Sequence[int]] = None) -> api.kp_fit_diagnosis:
         """kp_fit_diagnosis_batch: the engine's arrays, valid until the next call on it."""
         d = api.kp_fit_diagnosis()
@@ -695,6 +732,23 @@ class GenericScheduler:
             out.append(sr)
         b.close()
         return out
+
+    def schedule_changed(self, bindings: Sequence[dict]):
+        """schedule() for a requeue (patchScheduleResultForResourceBinding, scheduler.go:686-718):
+        (results, changed). results holds every binding's ScheduleResult with its status;
+        suggested_clusters is filled only for the bindings listed in `changed`, the ascending
+        indices of those whose placement differs from their spec.clusters as a set of
+        (name, replicas) pairs. The others keep the placement they hold: nothing to patch."""
+        b = Batch(self.snapshot, bindings)
+        try:
+            st, delta = b.schedule_delta()
+        finally:
+            b.close()
+        names = self.snapshot.names
+        out = [ScheduleResult(status=s, err=e, arg=a) for s, e, a in st]
+        for i, r in delta.items():
+            out[i].suggested_clusters = [TargetCluster(names[c], rep) for c, rep in r["targets"]]
+        return out, sorted(delta)
 
     def schedule_affinities_raw(self, structs, estimates=None, filters=None):
         """kp_schedule_affinities over packed kp_binding structs: (results dicts, affinity_index, attempts, rounds).
