@@ -696,6 +696,55 @@ int kp_batch_create_filters(kp_engine* e, const kp_snapshot* s, const kp_binding
                             kp_pack_cache* cache /* may be NULL */, const kp_estimates* est /* may be NULL */,
                             const kp_filter_answers* flt /* may be NULL */, kp_batch** out);
 
+/* ---- the scheduler's assumed workloads (SchedulingOvercommitProtection) -------------------
+ * With the gate on, the scheduler records every patched placement's footprint per cluster
+ * (updateAssumptionsCache, pkg/scheduler/scheduler.go:720-779) and every later Schedule call
+ * hands those footprints to the estimators as AssumedWorkloads (calAvailableReplicas,
+ * core/util.go:78-93; buildAssumedWorkloadsByCluster, core/estimation.go:115-139). The
+ * GeneralEstimator deducts them: pods and per-resource demand added to the summary's
+ * Allocating (deductAssumedWorkloadsFromSummary, estimator/client/general.go:110-151) and,
+ * on the model path, each workload placed first-fit over the model-grade nodes with
+ * SimulateScheduling(components, 1) before the request is counted (general.go:507-553).
+ * For one Schedule call the map is a constant input, as the snapshot is: a kp_assumptions
+ * deducts it once per cluster on the device, and a batch made over it answers over the
+ * deducted availability.
+ *
+ * kp_assumed_entry: one AssumedWorkload of one cluster. The entries of one cluster are
+ * deducted in the order given (the reference's order is a Go map iteration,
+ * GetAssumedWorkloads, cache.go:287: pass the list as it came, parity holds for that order);
+ * entries of different clusters may interleave. Nothing is retained after the call. */
+typedef struct kp_assumed_entry {
+  uint32_t cluster;             /* caller's cluster index (kp_snapshot_create order) */
+  const kp_component* components; /* Replicas + ResourceRequest; no NodeClaim: model nodes carry no
+                                     Node object, every one matches
+                                     (scheduling_simulator_components.go:149-153) */
+  uint32_t n_components;
+} kp_assumed_entry;
+typedef struct kp_assumptions kp_assumptions;
+/* n == 0 succeeds (the gate off: an empty map). KP_EINVAL for a cluster index at or beyond
+ * the snapshot's count, negative replicas and an unparsable quantity; KP_ENOTSUP for more
+ * than 16 components in one workload, a negative quantity, a cluster whose summed demand of
+ * one resource (or of pods) leaves int64, and a cluster whose residual model nodes need more
+ * node runs than min(its model node count, 4096); kp_last_error names the entry or cluster.
+ * The deduction is that of the snapshot's state at this call: after a kp_snapshot_update,
+ * kp_batch_create_assumed and the schedule calls of its batches return KP_ESTATE. */
+int kp_assumptions_create(kp_engine* e, const kp_snapshot* s, const kp_assumed_entry* entries, uint64_t n,
+                          kp_assumptions** out);
+/* Batches made over it keep what they need: it may be destroyed before them. */
+void kp_assumptions_destroy(kp_assumptions* a);
+/* kp_batch_create over the deducted availability: kp_schedule_batch, its _submit / _collect,
+ * _packed and _delta forms and kp_max_available_replicas answer with, at every cluster that
+ * has entries, the GeneralEstimator's answer over the deducted summary and model nodes (the
+ * value replaces the undeducted one; clusters without entries are untouched); filter, score
+ * and reasons do not change. a == NULL or made with n == 0: in every respect a
+ * kp_batch_create batch (nothing allocated, launched or waited for). KP_ENOTSUP for a
+ * binding that takes MaxAvailableComponentSets (multiple_pod_templates_scheduling on and
+ * isMultiTemplateSchedulingApplicable). Assumptions do not combine with
+ * kp_batch_create_estimates / _filters / _keyed, kp_schedule_affinities* or kp_multi_*:
+ * none of them takes a kp_assumptions. */
+int kp_batch_create_assumed(kp_engine* e, const kp_snapshot* s, const kp_assumptions* a, const kp_binding* bindings,
+                            uint64_t n, kp_batch** out);
+
 /* genericScheduler.Schedule for every binding of the batch. */
 int kp_schedule_batch(kp_engine* e, kp_batch* b, kp_results* out);
 /* kp_schedule_batch in two halves, for a caller that keeps batches in flight (a scheduler
@@ -867,7 +916,7 @@ int kp_max_available_replicas(kp_engine* e, kp_batch* b, uint64_t binding,
  * CustomizedClusterResourceModeling gate and models, the first-fit simulation over
  * the model-grade nodes (SchedulingSimulator.SimulateScheduling,
  * scheduling_simulator_components.go:51-131). Assumed workloads are empty
- * (SchedulingOvercommitProtection off). KP_ENOTSUP when the snapshot's options
+ * (kp_assumptions serve the single-template path only). KP_ENOTSUP when the snapshot's options
  * have the MultiplePodTemplatesScheduling gate off (the scheduler then never calls
  * it, core/util.go:113-118), or when a cluster's simulation exceeds the device
  * run capacity (kp_last_error says which). */

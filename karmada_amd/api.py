@@ -73,6 +73,10 @@ class kp_component(C.Structure):
                 ("resource_request", C.POINTER(kp_resource)), ("n_resource_request", u32)]
 
 
+class kp_assumed_entry(C.Structure):
+    _fields_ = [("cluster", u32), ("components", C.POINTER(kp_component)), ("n_components", u32)]
+
+
 class kp_binding(C.Structure):
     _fields_ = [
         ("uid", kp_str), ("api_version", kp_str), ("kind", kp_str), ("namespace_", kp_str), ("name", kp_str),
@@ -479,6 +483,15 @@ class World:
             out.append(kp_component(self.s(c.get("name", "")), int(c.get("replicas", 0)), 1 if rr is not None else 0,
                                     ra, nr))
         return self.arr(kp_component, out)
+
+    def assumed_entries(self, entries):
+        """[(cluster index, [component dicts as for components()])] -> (kp_assumed_entry array, n): the
+        AssumedWorkloads of buildAssumedWorkloadsByCluster, one entry per workload, in the order given."""
+        out = []
+        for cluster, comps in entries or []:
+            ca, nc = self.components(comps)
+            out.append(kp_assumed_entry(int(cluster), ca, nc))
+        return self.arr(kp_assumed_entry, out)
 
     def requirements(self, exprs):
         out = []

@@ -16,6 +16,7 @@
 
 #include "kp_dev.h"
 #include "kp_env.h"
+#include "kp_assume.h"
 #include "kp_sets.h"
 #include "kp_kernels.h"
 #include "kp_top.h"
@@ -315,6 +316,17 @@ int rows_from_class(stream_t, const SnapView& s, const BatchView& bv, const int3
   });
 }
 
+int assume_cluster(stream_t, const SnapView& s, const AssumedView& A) {
+  return grid("k_assume_cluster", A.n, assume_cluster_lds_bytes(),
+              [&](int a, unsigned char* sm) { body_assume_cluster(CpuBlk{(int64_t*)sm}, s, A, a); });
+}
+int est_assumed(stream_t, const SnapView& s, const BatchView& bv, const AssumedView& A, int mode, const int32_t* rep,
+                const uint64_t* fmask, int row0, int n_rows, int32_t* rows) {
+  if (A.n <= 0) return 0;
+  return grid("k_est_assumed", n_rows, est_assumed_lds_bytes(), [&](int row, unsigned char* sm) {
+    for (int a = 0; a < A.n; a++) body_est_assumed(CpuBlk{(int64_t*)sm}, s, bv, A, mode, rep, fmask, row0, row, a, rows);
+  });
+}
 int est_extra(stream_t, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
               const int32_t* extra, int32_t* rows) {
   return grid("k_est_extra", n, 0, [&](int blk, unsigned char* sm) {

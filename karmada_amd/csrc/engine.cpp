@@ -566,6 +566,10 @@ static int submit_rows(SubmitCtx& c) {
   const int B = bt->B, fast = c.fast;
   const bool bits = c.bits;
   dev::stream_t st = e->stream, sp = e->stream2;
+  if (bt->assumed && (bt->assumed->epoch != s->epoch || bt->assumed->updates != s->updates)) {
+    e->err = "the snapshot was updated after the batch's assumed workloads were deducted from it";
+    return KP_ESTATE;
+  }
   HIPCHK(dev::event_record(e->ev[EV_ROWS_BEGIN], sp));
   // component-set classes (BF_SETS bindings): their class rows (after the estimator
   // classes' rows, before k_class_order reads them all), and in the pair-row mode those
@@ -589,6 +593,13 @@ static int submit_rows(SubmitCtx& c) {
       KPROF(sp, "k_est_extra", bt->l_est_cls.size(), -1,
             dev::est_extra(sp, s->Cp, bt->d_est_cls, (int)bt->l_est_cls.size(), nullptr, bt->d_cls_est, bt->d_est_rows,
                            bt->cls_rows));
+    // the assumed workloads deducted at their clusters, written over the rows' entries before
+    // any reader (a batch with singleton classes has no class orders: its feasible-only rows
+    // are written after k_filter, and the correction follows them there)
+    if (bt->assumed && !single)
+      KPROF(sp, "k_est_assumed", bt->crep.size(), -1,
+            dev::est_assumed(sp, s->view, bt->view, bt->assumed->view, EA_CLASS, bt->d_crep, nullptr, 0,
+                             (int)bt->crep.size(), bt->cls_rows));
     HIPCHK(dev::event_record(e->ev[EV_CLASS_ROWS], sp));  // every class row is written (k_class_order's input)
     KPROF(sp, "k_filter", B, -1, dev::filter(sp, s->view, bt->view, bt->fmask));
     // the out-of-tree filter verdicts ANDed into their bindings' rows, ahead of every reader
@@ -600,6 +611,10 @@ static int submit_rows(SubmitCtx& c) {
       KPROF(sp, est_class_feasible_name(fast), bt->l_cls_single.size(), -1,
             dev::est_class(sp, s->view, bt->view, bt->d_crep, (int)bt->l_cls_single.size(), bt->cls_rows, fast,
                            bt->d_cls_single, bt->fmask));
+    if (bt->assumed && single)
+      KPROF(sp, "k_est_assumed", bt->crep.size(), -1,
+            dev::est_assumed(sp, s->view, bt->view, bt->assumed->view, EA_CLASS, bt->d_crep, nullptr, 0,
+                             (int)bt->crep.size(), bt->cls_rows));
   } else {
     const int md_cap = md_cap_of(s);
     KPROF(sp, pair_name(fast), B, -1,
@@ -622,6 +637,10 @@ static int submit_rows(SubmitCtx& c) {
     if (!bt->l_est_cls.empty())
       KPROF(sp, "k_est_extra", B, -1,
             dev::est_extra(sp, s->Cp, nullptr, B, bt->d_bcls, bt->d_cls_est, bt->d_est_rows, bt->est));
+    // pair-row mode: the bindings' own rows at the assumed clusters, as the pair kernel writes them
+    if (bt->assumed)
+      KPROF(sp, "k_est_assumed", B, -1,
+            dev::est_assumed(sp, s->view, bt->view, bt->assumed->view, EA_MERGED, nullptr, bt->fmask, 0, B, bt->est));
   }
   if (c.orders) {
     // k_class_order reads only the class rows (k_est_class), so it runs on stream3 beside
@@ -1796,6 +1815,9 @@ static int max_available_replicas_impl(kp_engine* e, kp_batch* bt, uint64_t bind
   kp_snapshot* s = bt->snap;
   int rc = run_pair(e, bt, nullptr, 1, (int)binding, 1);
   if (rc) return rc;
+  if (bt->assumed)  // the answer over the deducted availability
+    HIPCHK(dev::est_assumed(e->stream, s->view, bt->view, bt->assumed->view, EA_RAW, nullptr, nullptr, (int)binding, 1,
+                            bt->est));
   std::vector<int32_t> row(s->Cp);
   HIPCHK(dev::d2h(row.data(), bt->est + (size_t)binding * s->Cp, 4 * (size_t)s->Cp, e->stream));
   HIPCHK(dev::sync(e->stream));

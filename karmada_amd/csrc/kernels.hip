@@ -19,6 +19,7 @@
 #include "kp_dev.h"
 #include "kp_env.h"
 #include "kp_kernels.h"
+#include "kp_assume.h"
 #include "kp_sets.h"
 #include "kp_top.h"
 
@@ -468,6 +469,33 @@ extern "C" __global__ void __launch_bounds__(64 * kFilterWaves) k_flt_rows_rank(
   const int i = (int)(blockIdx.x * kFilterWaves) + kp_uniform((int)(threadIdx.x >> 6));
   if (i >= n_rows * W) return;  // wave-uniform
   body_flt_rows_rank(GpuBlk{nullptr}, i / W, i % W, C, W, perm, src, dst);
+}
+#else
+;
+#endif
+// kp_assume.h: one wave64 per cluster with entries; one wave64 per (row, assumed cluster),
+// kEstAssumedWaves per workgroup, the item index through a scalar register.
+extern "C" __global__ void __launch_bounds__(64) k_assume_cluster(SnapView s, AssumedView A)
+#if KP_K(8)
+{
+  KP_SMEM;
+  body_assume_cluster(WaveBlk{(int64_t*)smem}, s, A, (int)blockIdx.x);
+}
+#else
+;
+#endif
+extern "C" __global__ void __launch_bounds__(64 * kEstAssumedWaves) k_est_assumed(SnapView s, BatchView bv, AssumedView A,
+                                                                                  int mode, const int32_t* rep,
+                                                                                  const uint64_t* fmask, int row0,
+                                                                                  int n_rows, int32_t* rows)
+#if KP_K(8)
+{
+  KP_SMEM;
+  const int wv = kp_uniform((int)(threadIdx.x >> 6));
+  const int64_t i = (int64_t)blockIdx.x * kEstAssumedWaves + wv;
+  if (i >= (int64_t)n_rows * A.n) return;  // wave-uniform
+  body_est_assumed(WaveBlk{(int64_t*)smem + 2 * wv}, s, bv, A, mode, rep, fmask, row0, (int)(i / A.n), (int)(i % A.n),
+                   rows);
 }
 #else
 ;
@@ -1069,6 +1097,23 @@ int flt_rows_rank(stream_t st, const SnapView& s, const uint64_t* src, int n_row
   if (items > INT32_MAX) return chk(hipErrorInvalidValue);
   hipLaunchKernelGGL(k_flt_rows_rank, dim3((unsigned)((items + kFilterWaves - 1) / kFilterWaves)),
                      dim3(64 * kFilterWaves), 0, (hipStream_t)st, n_rows, s.C, s.W, s.perm, src, dst);
+  return chk(hipGetLastError());
+}
+
+int assume_cluster(stream_t st, const SnapView& s, const AssumedView& A) {
+  if (A.n <= 0) return 0;
+  hipLaunchKernelGGL(k_assume_cluster, dim3(A.n), dim3(64), assume_cluster_lds_bytes(), (hipStream_t)st, s, A);
+  return chk(hipGetLastError());
+}
+
+int est_assumed(stream_t st, const SnapView& s, const BatchView& bv, const AssumedView& A, int mode, const int32_t* rep,
+                const uint64_t* fmask, int row0, int n_rows, int32_t* rows) {
+  const int64_t items = (int64_t)n_rows * A.n;
+  if (items <= 0) return 0;
+  const int64_t blocks = (items + kEstAssumedWaves - 1) / kEstAssumedWaves;
+  if (blocks > INT32_MAX) return chk(hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_est_assumed, dim3((unsigned)blocks), dim3(64 * kEstAssumedWaves), est_assumed_lds_bytes(),
+                     (hipStream_t)st, s, bv, A, mode, rep, fmask, row0, n_rows, rows);
   return chk(hipGetLastError());
 }
 

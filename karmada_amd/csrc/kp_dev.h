@@ -21,6 +21,7 @@ struct NodeEstArgs;
 struct NodeView;
 struct ClaimProg;
 struct NodeSetsArgs;
+struct AssumedView;
 namespace dev {
 
 typedef void* stream_t;
@@ -118,6 +119,13 @@ int rows_from_class(stream_t st, const SnapView& s, const BatchView& bv, const i
 // order, -1 = no answer; negative cls_est: the row is left alone).
 int est_extra(stream_t st, int Cp, const int32_t* list, int n, const int32_t* bcls, const int32_t* cls_est,
               const int32_t* extra, int32_t* rows);
+// kp_assumptions_create: the n clusters of A (body_assume_cluster, one wave each): their
+// Allocating sums, pods, residual model-node runs and status.
+int assume_cluster(stream_t st, const SnapView& s, const AssumedView& A);
+// An assumed batch's estimate rows corrected at A's clusters (body_est_assumed), one wave per
+// (row, cluster): rows [row0, row0 + n_rows) of rows[..][Cp] in mode EA_* (kp_assume.h).
+int est_assumed(stream_t st, const SnapView& s, const BatchView& bv, const AssumedView& A, int mode, const int32_t* rep,
+                const uint64_t* fmask, int row0, int n_rows, int32_t* rows);
 // kp_schedule_affinities_ex: a call's answer rows, uploaded in caller cluster order, into rank
 // order (body_est_rows_rank, body_flt_rows_rank). src[n_rows][C] -> dst[n_rows][Cp] with -1
 // in the padding; src[n_rows][ceil(C/64)] -> dst[n_rows][W] words with zero bits there.

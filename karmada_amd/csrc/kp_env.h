@@ -26,6 +26,7 @@
 //   KP_ORDER_AMORT           4         batch    test     bindings per estimator class below which a batch builds no class orders
 //   KP_EST_SINGLE            1         process  tuning   0: singleton estimator classes keep whole rows
 //   KP_SETS_RUNS_CAP         4096      batch    test     node runs per cluster of the component-set simulation (lowered only)
+//   KP_ASSUME_RUNS_CAP       4096      call     test     node runs per cluster of kp_assumptions_create's deduction (lowered only)
 //   KP_PACK_THREADS          (cpus)    batch    test     host threads that pack a batch
 //   KP_PACK_TIMING           unset     batch    tuning   set: kp_batch_create prints its phase times to stderr
 //   KP_PAIR_GENERIC          unset     call     test     set: the generic pair kernel whatever the snapshot allows

@@ -33,6 +33,7 @@
 #include "kp_layout.h"
 #include "kp_launch.h"
 #include "kp_sets.h"  // (the one device-body header here: kp_batch holds SetsArgs by value)
+#include "kp_assume.h"  // (AssumedView alone: kp_assumptions holds it by value)
 
 using namespace kp;
 
@@ -445,6 +446,7 @@ void prof_fold(kp_engine* e, const uint32_t* h_stats);
 struct kp_snapshot {
   kp_engine* e = nullptr;
   uint64_t epoch = next_snap_epoch();
+  uint64_t updates = 0;  // kp_snapshot_update calls applied (a kp_assumptions holds the state it deducted from)
   kp_options opts{};
   int C = 0, Cp = 0, W = 0;
   Dict str, keys, gvk, res, regions;
@@ -465,6 +467,20 @@ struct kp_snapshot {
   std::vector<uint64_t> api_bits;
   Arena dev;
   SnapView view{};
+};
+
+// The assumed workloads deducted once per cluster (assumed.cpp; kp_assume.h): the device
+// arrays of `view`, the snapshot state they were deducted from, and the clusters' caller
+// indices for the error texts. A batch made over it shares it (kp_batch::assumed).
+struct AssumedState {
+  Arena dev;
+  AssumedView view{};
+  const kp_snapshot* snap = nullptr;
+  uint64_t epoch = 0, updates = 0;
+};
+struct kp_assumptions {
+  kp_engine* e = nullptr;
+  std::shared_ptr<const AssumedState> st;  // null: no entries (the gate is off)
 };
 
 // diagnostic builds: phase stamps and counters, kDbgSlots x kDbgSpread (kp_select.h)
@@ -532,6 +548,10 @@ struct kp_batch {
   // whoever else was created over the same answers (kp_schedule_affinities_ex: one batch a
   // round) and which goes back to the pool with the last of them; null for a batch without.
   std::shared_ptr<const AnswerRows> rows;
+  // The assumed workloads' deducted state (kp_batch_create_assumed; null for every other
+  // batch, which launches nothing for it): k_est_assumed rewrites the estimate rows at its
+  // clusters in every schedule call.
+  std::shared_ptr<const AssumedState> assumed;
   // component-set classes (BF_SETS): class id and resolved component list of each;
   // their rows are MaxAvailableComponentSets per cluster (k_sets_rows), and in the
   // pair-row mode the BF_SETS bindings' rows are rebuilt from them (k_rows_from_class)

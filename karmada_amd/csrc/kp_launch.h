@@ -178,6 +178,11 @@ KP_HD inline size_t fit_hist_lds_bytes() { return 4 * (size_t)kTsetRowsMax; }
 // k_changed_long (body_changed_long): the result's replicas by cluster rank and a presence
 // bit per cluster (77 848 bytes at the 18 624-cluster ceiling).
 KP_HD inline size_t changed_lds_bytes(int Cp) { return kRedBytes + 4 * (size_t)Cp + 4 * (size_t)((Cp + 31) >> 5); }
+// k_assume_cluster / k_est_assumed (kp_assume.h): one wave per item, the runs in global
+// scratch; the waves' reduction slots only.
+constexpr int kEstAssumedWaves = 4;  // (row, assumed cluster) items per workgroup
+KP_HD inline size_t assume_cluster_lds_bytes() { return 16; }
+KP_HD inline size_t est_assumed_lds_bytes() { return 16 * (size_t)kEstAssumedWaves; }
 // k_slow (body_slow): target bits, lds_area bytes for the small serial problems, lds_sort
 // for the candidate sorts.
 KP_HD inline size_t slow_lds_bytes(int Cp, int lds_area, int lds_sort) {

@@ -766,6 +766,7 @@ int kp_snapshot_update(kp_engine* e, kp_snapshot* s, const kp_cluster* clusters,
                     s->res.names.size() != n_res || s->regions.names != regions0;
   if (dict_grew) *dict_grew = grew ? 1 : 0;
   if (grew) s->epoch = next_snap_epoch();  // (packed records resolved against the old dictionaries)
+  s->updates++;
   s->dev.reset();
   return upload_snapshot(e, s);
 }

@@ -45,6 +45,7 @@ EXPORTS = (
     "kp_model_grades", "kp_node_max_replicas", "kp_node_max_component_sets", "kp_last_stage_times",
     "kp_engine_set_threads", "kp_snapshot_replicate", "kp_engine_set_profile", "kp_last_kernel_times",
     "kp_watch_create", "kp_watch_destroy", "kp_affected_bindings",
+    "kp_assumptions_create", "kp_assumptions_destroy", "kp_batch_create_assumed",
     "kp_multi_create", "kp_multi_destroy", "kp_multi_last_error", "kp_multi_devices", "kp_multi_engine",
     "kp_multi_snapshot_create", "kp_multi_snapshot_update", "kp_multi_snapshot_destroy", "kp_multi_snapshot_replica",
     "kp_multi_shard_cuts", "kp_multi_batch_create", "kp_multi_batch_destroy", "kp_multi_batch_shards",
@@ -88,6 +89,10 @@ def load_library(path: str = LIB_PATH):
     L.kp_batch_create_filters.argtypes = [vp, vp, C.POINTER(api.kp_binding), C.POINTER(api.kp_binding_key),
                                           C.c_uint64, vp, C.POINTER(api.kp_estimates),
                                           C.POINTER(api.kp_filter_answers), C.POINTER(vp)]
+    L.kp_assumptions_create.argtypes = [vp, vp, C.POINTER(api.kp_assumed_entry), C.c_uint64, C.POINTER(vp)]
+    L.kp_assumptions_destroy.argtypes = [vp]
+    L.kp_assumptions_destroy.restype = None
+    L.kp_batch_create_assumed.argtypes = [vp, vp, vp, C.POINTER(api.kp_binding), C.c_uint64, C.POINTER(vp)]
     L.kp_schedule_batch.argtypes = [vp, vp, C.POINTER(api.kp_results)]
     L.kp_schedule_batch_submit.argtypes = [vp, vp]
     L.kp_schedule_batch_collect.argtypes = [vp, vp, C.POINTER(api.kp_results)]
@@ -356,6 +361,34 @@ class PackCache:
             pass
 
 
+class Assumptions:
+    """The scheduler's assumed workloads deducted once per cluster (kp_assumptions): `entries` is
+    [(cluster index or name, [component dicts])], one per AssumedWorkload, each cluster's in the
+    order they are to be deducted. An empty list is the gate off."""
+
+    def __init__(self, snap: Snapshot, entries: Sequence[tuple] = ()):
+        self.snap = snap
+        eng = snap.engine
+        idx = {n: i for i, n in enumerate(snap.names)}
+        w = api.World()
+        ea, n = w.assumed_entries([(idx[c] if isinstance(c, str) else c, comps) for c, comps in entries])
+        h = C.c_void_p()
+        eng._check(eng.L.kp_assumptions_create(eng.h, snap.h, ea, n, C.byref(h)), "kp_assumptions_create")
+        self.h = h
+        self.n = n
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.snap.engine.L.kp_assumptions_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """A batch of ResourceBindings packed against one snapshot (kp_batch). With `cache`
     and `keys` ((uid, generation) per binding, api.binding_keys) it is created through
@@ -366,12 +399,19 @@ class Batch:
     n_plugins) it is created through kp_batch_create_filters (together with `estimates`, if
     given): rows is a bool array [R, C] of the out-of-tree filter plugins' ANDed verdicts
     (caller cluster order, True = passed), row_of each binding's row (-1: no plugin
-    objected), n_plugins the number of registered out-of-tree plugins they fold in."""
+    objected), n_plugins the number of registered out-of-tree plugins they fold in. With
+    `assumed` (an Assumptions) it is created through kp_batch_create_assumed and answers over
+    the deducted availability; the engine has no entry point that combines assumptions with
+    a cache, estimates or filters, so that is refused here (EngineError, KP_ENOTSUP)."""
 
     def __init__(self, snap: Snapshot, bindings: Sequence[dict] = (), structs=None, cache: "PackCache" = None,
-                 keys=None, generations: Sequence[int] = None, estimates=None, filters=None):
+                 keys=None, generations: Sequence[int] = None, estimates=None, filters=None,
+                 assumed: "Assumptions" = None):
         self.snap = snap
         eng = snap.engine
+        if assumed is not None and (cache is not None or estimates is not None or filters is not None):
+            raise EngineError(f"kp_batch_create_assumed: rc={KP_ENOTSUP}: assumed workloads do not combine with a "
+                              "pack cache, estimates or filter answers")
         if structs is None:
             w = api.World()
             ba, n = w.bindings(bindings)
@@ -388,7 +428,10 @@ class Batch:
             if len(row_of) != n:
                 raise ValueError(f"estimates: row_of has {len(row_of)} entries for {n} bindings")
             est, self._est = api.estimates(rows, row_of)
-        if filters is not None:
+        if assumed is not None:
+            eng._check(eng.L.kp_batch_create_assumed(eng.h, snap.h, assumed.h, ba, n, C.byref(h)),
+                       "kp_batch_create_assumed")
+        elif filters is not None:
             rows, row_of, n_plugins = filters
             if len(row_of) != n:
                 raise ValueError(f"filters: row_of has {len(row_of)} entries for {n} bindings")
@@ -722,8 +765,10 @@ class GenericScheduler:
     def __init__(self, engine: Engine, clusters: Sequence[dict], opts: Optional[api.kp_options] = None):
         self.snapshot = Snapshot(engine, clusters, opts)
 
-    def schedule(self, bindings: Sequence[dict]) -> List[ScheduleResult]:
-        b = Batch(self.snapshot, bindings)
+    def schedule(self, bindings: Sequence[dict], assumed: "Assumptions" = None) -> List[ScheduleResult]:
+        """Schedule for every binding; with `assumed` (an Assumptions over this snapshot) over the
+        availability left after the scheduler's assumed workloads."""
+        b = Batch(self.snapshot, bindings, assumed=assumed)
         out = []
         names = self.snapshot.names
         for r in b.schedule():
@@ -733,13 +778,13 @@ class GenericScheduler:
         b.close()
         return out
 
-    def schedule_changed(self, bindings: Sequence[dict]):
+    def schedule_changed(self, bindings: Sequence[dict], assumed: "Assumptions" = None):
         """schedule() for a requeue (patchScheduleResultForResourceBinding, scheduler.go:686-718):
         (results, changed). results holds every binding's ScheduleResult with its status;
         suggested_clusters is filled only for the bindings listed in `changed`, the ascending
         indices of those whose placement differs from their spec.clusters as a set of
         (name, replicas) pairs. The others keep the placement they hold: nothing to patch."""
-        b = Batch(self.snapshot, bindings)
+        b = Batch(self.snapshot, bindings, assumed=assumed)
         try:
             st, delta = b.schedule_delta()
         finally:
@@ -899,9 +944,11 @@ class GenericScheduler:
                    "kp_max_available_component_sets")
         return [int(out[i]) for i in range(len(clusters))]
 
-    def max_available_replicas(self, binding: dict, clusters: Sequence[str]) -> List[int]:
-        """GeneralEstimator.MaxAvailableReplicas for one binding's request."""
-        b = Batch(self.snapshot, [binding])
+    def max_available_replicas(self, binding: dict, clusters: Sequence[str],
+                               assumed: "Assumptions" = None) -> List[int]:
+        """GeneralEstimator.MaxAvailableReplicas for one binding's request (with `assumed`: after
+        the assumed workloads are deducted)."""
+        b = Batch(self.snapshot, [binding], assumed=assumed)
         eng = self.snapshot.engine
         idx = {n: i for i, n in enumerate(self.snapshot.names)}
         ci = (C.c_uint32 * max(1, len(clusters)))(*[idx[n] for n in clusters])

@@ -677,6 +677,83 @@ static int run_watch(kp_engine* e) {
   return bad ? 1 : 0;
 }
 
+// kp_assumptions_create and kp_batch_create_assumed (assumed.cpp; kp_assume.h) over a universe
+// with model clusters: entries on every third cluster, among them a long list, a workload
+// that splits runs and one without components; the assumed batch scheduled on the class rows
+// and under KP_PAIR_ROWS=1 (both must place alike), an n == 0 handle against the plain batch,
+// then the run-capacity refusal.
+static int run_assumed(kp_engine* e) {
+  kps_world* w = nullptr;
+  const uint32_t C = 130;
+  if (kps_create(6, 13, C, 0, 400, &w)) return 1;
+  uint64_t nc = 0, nb = 0;
+  const kp_cluster* cl = kps_clusters(w, &nc);
+  const kp_binding* bs = kps_bindings(w, &nb);
+  kp_options o{};
+  o.customized_cluster_resource_modeling = 1;
+  o.enabled_plugins = KP_PLUGIN_ALL;
+  const char *cpu = "cpu", *mem = "memory", *q1 = "750m", *q2 = "1Gi";
+  kp_resource rq[2] = {{{cpu, 3}, {q1, 4}}, {{mem, 6}, {q2, 3}}};
+  kp_component comps[3] = {};
+  comps[0].replicas = 3;
+  comps[0].has_replica_requirements = 1;
+  comps[0].resource_request = rq;
+  comps[0].n_resource_request = 2;
+  comps[1].replicas = 2;
+  comps[2].replicas = 0;
+  std::vector<kp_assumed_entry> en;
+  for (uint32_t c = 0; c < C; c += 3)
+    for (int k = 0; k < (c == 63 ? 200 : 3); k++) en.push_back(kp_assumed_entry{c, comps, (uint32_t)(k % 4)});
+  kp_snapshot* s = nullptr;
+  kp_assumptions *a = nullptr, *a0 = nullptr, *a1 = nullptr;
+  kp_batch *b = nullptr, *b0 = nullptr, *bp = nullptr;
+  int bad = 0;
+  if (kp_snapshot_create(e, cl, nc, &o, &s) || kp_assumptions_create(e, s, en.data(), en.size(), &a) ||
+      kp_assumptions_create(e, s, nullptr, 0, &a0) || kp_batch_create_assumed(e, s, a, bs, nb, &b) ||
+      kp_batch_create_assumed(e, s, a0, bs, nb, &b0) || kp_batch_create(e, s, bs, nb, &bp)) {
+    fprintf(stderr, "assumed: engine error: %s\n", kp_last_error(e));
+    bad = 1;
+  }
+  auto flat = [](const kp_results& r) {
+    std::vector<int64_t> v(r.status, r.status + r.n_bindings);
+    const size_t t0 = v.size();
+    for (uint64_t i = 0; i < r.n_targets; i++) v.push_back(((int64_t)r.cluster_idx[i] << 32) | (uint32_t)r.replicas[i]);
+    for (uint64_t b = 0; b < r.n_bindings; b++)  // (a binding's targets compare as a multiset)
+      std::sort(v.begin() + t0 + r.offsets[b], v.begin() + t0 + r.offsets[b + 1]);
+    return v;
+  };
+  if (!bad) {
+    kp_results r{};
+    std::vector<int64_t> rows, cls, plain, none;
+    bad += kp_schedule_batch(e, b, &r) != 0;
+    cls = flat(r);
+    setenv("KP_PAIR_ROWS", "1", 1);
+    bad += kp_schedule_batch(e, b, &r) != 0;
+    rows = flat(r);
+    unsetenv("KP_PAIR_ROWS");
+    bad += kp_schedule_batch(e, bp, &r) != 0;
+    plain = flat(r);
+    bad += kp_schedule_batch(e, b0, &r) != 0;
+    none = flat(r);
+    if (cls != rows || plain != none || cls == plain) {
+      fprintf(stderr, "assumed: class rows %s pair rows, n == 0 %s plain, assumed %s plain\n", cls == rows ? "==" : "!=",
+              plain == none ? "==" : "!=", cls == plain ? "==" : "!=");
+      bad++;
+    }
+    setenv("KP_ASSUME_RUNS_CAP", "1", 1);
+    if (kp_assumptions_create(e, s, en.data(), en.size(), &a1) != KP_ENOTSUP) bad++;
+    unsetenv("KP_ASSUME_RUNS_CAP");
+  }
+  for (kp_batch* x : {b, b0, bp})
+    if (x) kp_batch_destroy(x);
+  for (kp_assumptions* x : {a, a0, a1})
+    if (x) kp_assumptions_destroy(x);
+  if (s) kp_snapshot_destroy(s);
+  kps_destroy(w);
+  printf("assumed: %llu bindings x %u clusters, %zu entries, %d mismatches\n", (unsigned long long)nb, C, en.size(), bad);
+  return bad ? 1 : 0;
+}
+
 // `driver ceiling`: the snapshots at which a workgroup's LDS is full (tests/test_lds_ceiling.py:
 // 18 624 clusters without spread bindings, 14 336 with them, and the class-order switch at
 // 16 384 / 16 385) instead of the small universes, so the sanitizer sees every global array
@@ -700,6 +777,7 @@ int main(int argc, char** argv) {
   if (!ceiling) fails += run_batch_answers(e);
   if (!ceiling) fails += run_pack_stages(e);
   if (!ceiling) fails += run_watch(e);
+  if (!ceiling) fails += run_assumed(e);
   kp_engine_destroy(e);
   printf("%s\n", fails ? "FAIL" : "ok");
   return fails ? 1 : 0;
