@@ -1,8 +1,12 @@
 // blk_selftest.hip — test-only library (libkp_blktest.so): checks every GpuBlk
 // primitive (kp_blk.h) on the device against a host computation, for several
 // workgroup sizes and seeded random inputs; and runs the row-ranking kernel bodies of
-// kp_kernels.h over caller-given rows. Never linked into libkp.so.
+// kp_kernels.h over caller-given rows; and runs webster_par (kp_select.h) over caller-given
+// party lists at every block shape, reporting the exit each list took. Never linked into
+// libkp.so.
 #include <hip/hip_runtime.h>
+
+#define KP_EXIT_MARKS 1  // kp_select.h: webster_par's exit marks (this library only)
 
 #include <cstdio>
 #include <cstring>
@@ -305,6 +309,176 @@ extern "C" int kp_webster_reg_selftest(const int64_t* votes, const int32_t* offs
   int declined = 0;
   for (int j = 0; j < nl; j++) declined += ok[j] ? 0 : 1;
   return declined;
+}
+
+// ---------------------------------------------------------------------------
+// webster_par (kp_select.h), one block per list. List j = parties [offs[j], offs[j+1])
+// with int32 votes in [0, 2^31) and a rank each, Ns[j] seats, the name order descs[j].
+// SelScratch is laid out as carve_sel_scratch lays it out (whist 2 KB, hist 1 KB, buf)
+// with `cap` entries of buf. pre != 0: the caller's first pass is done here and handed
+// over as a WebPre (totals, the octave histogram in sc.hist, web_ctr zeroed), the
+// contract of kp_paths.h; pre == 0: webster_par takes its own.
+// Per party: web_seats. Per list: info[5] = mode, compact, np, Lb, exit marks (WebExit);
+// and, when compact, the np entries of w.pl as (rank, seats) pairs in list order
+// (pl_rank / pl_seats at [offs[j], offs[j] + np)), read after the return.
+// ---------------------------------------------------------------------------
+KP_HD inline size_t wpar_sel_bytes(int cap) { return 2048 + 1024 + 8 * (size_t)cap; }
+template <class BLK>
+KP_FI void body_webster_par_test(const BLK& B, unsigned char* sel, int cap, int pre, const int32_t* votes,
+                                 const uint32_t* ranks, int n, int32_t N, bool desc, int32_t* seats,
+                                 uint32_t* pl_rank, int32_t* pl_seats, int64_t* info) {
+  SelScratch ss;
+  ss.whist = (unsigned long long*)sel;
+  ss.hist = (uint32_t*)(ss.whist + 256);
+  ss.buf = (uint64_t*)(ss.hist + 256);
+  ss.cap = cap;
+  ss.dbg = (unsigned long long*)(info + 4);
+  auto parties = [&](auto fn) {
+    for (int i = B.tid(); i < n; i += B.nth()) fn(ranks[i], (int64_t)votes[i]);
+  };
+  WebPre wp{0, 0, 0};
+  if (pre) {
+    for (int i = B.tid(); i < 256; i += B.nth()) ss.hist[i] = 0;
+    if (B.tid() == 0) *web_ctr(ss) = 0;
+    B.sync();
+    int64_t V = 0, vmax = 0, P = 0, none = 0;
+    parties([&](uint32_t, int64_t v) {
+      V += v;
+      if (v > vmax) vmax = v;
+      if (v > 0) {
+        P++;
+        kp_atomic_add(&ss.hist[vote_bin((uint32_t)v)], 1u);
+      }
+    });
+    auto add = [](int64_t p, int64_t q) { return p + q; };
+    B.reduce4(V, add, 0, P, add, 0, vmax, [](int64_t p, int64_t q) { return p > q ? p : q; }, INT64_MIN, none, add, 0);
+    wp.V = V;
+    wp.vmax = vmax;
+    wp.P = P;
+  }
+  const WebRes w = webster_par(B, parties, N, desc, ss, pre ? &wp : nullptr);
+  for (int i = B.tid(); i < n; i += B.nth()) seats[i] = web_seats(w, (int64_t)votes[i], ranks[i]);
+  if (w.mode == 2 && w.compact)
+    for (int i = B.tid(); i < w.np && i < n; i += B.nth()) {
+      const uint64_t e = w.pl[i];
+      pl_rank[i] = (uint32_t)(e >> 32);
+      pl_seats[i] = web_seats(w, (int64_t)(uint32_t)e, (uint32_t)(e >> 32));
+    }
+  if (B.tid() == 0) {
+    info[0] = w.mode;
+    info[1] = w.compact ? 1 : 0;
+    info[2] = w.np;
+    info[3] = w.Lb;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(1024) k_webster_par_test(int cap, int pre, const int32_t* votes,
+                                                                      const uint32_t* ranks, const int32_t* offs,
+                                                                      const int32_t* Ns, const int32_t* descs,
+                                                                      int32_t* seats, uint32_t* pl_rank,
+                                                                      int32_t* pl_seats, int64_t* info) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int j = (int)blockIdx.x, a = offs[j];
+  body_webster_par_test(GpuBlk{(int64_t*)smem}, smem + kRedBytes, cap, pre, votes + a, ranks + a, offs[j + 1] - a,
+                        Ns[j], descs[j] != 0, seats + a, pl_rank + a, pl_seats + a, info + 5 * (size_t)j);
+}
+// one wave alone on its list, as k_select_top's waves run webster_par
+extern "C" __global__ void __launch_bounds__(64) k_webster_par_wave_test(int cap, int pre, const int32_t* votes,
+                                                                         const uint32_t* ranks, const int32_t* offs,
+                                                                         const int32_t* Ns, const int32_t* descs,
+                                                                         int32_t* seats, uint32_t* pl_rank,
+                                                                         int32_t* pl_seats, int64_t* info) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int j = (int)blockIdx.x, a = offs[j];
+  body_webster_par_test(WaveBlk{(int64_t*)smem}, smem + 64, cap, pre, votes + a, ranks + a, offs[j + 1] - a, Ns[j],
+                        descs[j] != 0, seats + a, pl_rank + a, pl_seats + a, info + 5 * (size_t)j);
+}
+
+// gpu: 0 the host block (CpuBlk), 1 GpuBlk with nth threads (64 .. 1024, a multiple of 64),
+// 2 WaveBlk (one wave; nth ignored). seats_out / pl_rank / pl_seats: offs[nl] entries
+// (pl_* are 0xFF.. / -1 where nothing was written); info: 5 int64 per list. Returns 0, or
+// -1 with msg on a bad argument or a HIP error.
+extern "C" int kp_webster_par_selftest(int gpu, int nth, int cap, int pre, const int32_t* votes, const uint32_t* ranks,
+                                       const int32_t* offs, const int32_t* Ns, const int32_t* descs, int nl,
+                                       int32_t* seats_out, uint32_t* pl_rank, int32_t* pl_seats, int64_t* info,
+                                       char* msg, int msg_len) {
+  const int total = offs[nl];
+  if (cap < 0 || cap > 4096 || gpu < 0 || gpu > 2 || (gpu == 1 && (nth < 64 || nth > 1024 || nth % 64))) {
+    snprintf(msg, msg_len, "bad argument: gpu=%d nth=%d cap=%d", gpu, nth, cap);
+    return -1;
+  }
+  for (int j = 0; j < nl; j++)
+    if (offs[j + 1] < offs[j]) {
+      snprintf(msg, msg_len, "bad offsets at list %d", j);
+      return -1;
+    }
+  memset(pl_rank, 0xFF, 4 * (size_t)total);
+  memset(pl_seats, 0xFF, 4 * (size_t)total);
+  memset(info, 0, 8 * 5 * (size_t)nl);
+  if (!gpu) {
+    std::vector<uint64_t> mem((kRedBytes + wpar_sel_bytes(cap)) / 8 + 1);
+    unsigned char* sm = (unsigned char*)mem.data();
+    for (int j = 0; j < nl; j++) {
+      const int a = offs[j];
+      body_webster_par_test(CpuBlk{(int64_t*)sm}, sm + kRedBytes, cap, pre, votes + a, ranks + a, offs[j + 1] - a, Ns[j],
+                            descs[j] != 0, seats_out + a, pl_rank + a, pl_seats + a, info + 5 * (size_t)j);
+    }
+    return 0;
+  }
+  int32_t *dv, *doffs, *dN, *dd, *ds, *dps;
+  uint32_t *dr, *dpr;
+  int64_t* di;
+  const size_t tb = 4 * (size_t)(total + 1);
+  if (hipMalloc(&dv, tb) || hipMalloc(&dr, tb) || hipMalloc(&doffs, 4 * (size_t)(nl + 1)) ||
+      hipMalloc(&dN, 4 * (size_t)nl + 4) || hipMalloc(&dd, 4 * (size_t)nl + 4) || hipMalloc(&ds, tb) ||
+      hipMalloc(&dpr, tb) || hipMalloc(&dps, tb) || hipMalloc(&di, 8 * 5 * (size_t)nl + 8)) {
+    snprintf(msg, msg_len, "hipMalloc failed");
+    return -1;
+  }
+  (void)hipMemcpy(dv, votes, 4 * (size_t)total, hipMemcpyHostToDevice);
+  (void)hipMemcpy(dr, ranks, 4 * (size_t)total, hipMemcpyHostToDevice);
+  (void)hipMemcpy(doffs, offs, 4 * (size_t)(nl + 1), hipMemcpyHostToDevice);
+  (void)hipMemcpy(dN, Ns, 4 * (size_t)nl, hipMemcpyHostToDevice);
+  (void)hipMemcpy(dd, descs, 4 * (size_t)nl, hipMemcpyHostToDevice);
+  (void)hipMemset(ds, 0xFF, tb);
+  (void)hipMemset(dpr, 0xFF, tb);
+  (void)hipMemset(dps, 0xFF, tb);
+  (void)hipMemset(di, 0, 8 * 5 * (size_t)nl + 8);
+  const size_t smem = (gpu == 1 ? kRedBytes : 64) + wpar_sel_bytes(cap);
+  int rc = 0;
+  if (nl > 0) {
+    if (gpu == 1) {
+      if (smem > 65536)
+        (void)hipFuncSetAttribute((const void*)k_webster_par_test, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      hipLaunchKernelGGL(k_webster_par_test, dim3(nl), dim3(nth), smem, 0, cap, pre, dv, dr, doffs, dN, dd, ds, dpr, dps,
+                         di);
+    } else {
+      if (smem > 65536)
+        (void)hipFuncSetAttribute((const void*)k_webster_par_wave_test, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)smem);
+      hipLaunchKernelGGL(k_webster_par_wave_test, dim3(nl), dim3(64), smem, 0, cap, pre, dv, dr, doffs, dN, dd, ds, dpr,
+                         dps, di);
+    }
+  }
+  if (hipDeviceSynchronize() != hipSuccess) {
+    snprintf(msg, msg_len, "kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  } else {
+    (void)hipMemcpy(seats_out, ds, 4 * (size_t)total, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(pl_rank, dpr, 4 * (size_t)total, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(pl_seats, dps, 4 * (size_t)total, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(info, di, 8 * 5 * (size_t)nl, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dv);
+  (void)hipFree(dr);
+  (void)hipFree(doffs);
+  (void)hipFree(dN);
+  (void)hipFree(dd);
+  (void)hipFree(ds);
+  (void)hipFree(dpr);
+  (void)hipFree(dps);
+  (void)hipFree(di);
+  return rc;
 }
 
 // The two row-ranking kernels of kp_schedule_affinities_ex (kp_kernels.h body_est_rows_rank,

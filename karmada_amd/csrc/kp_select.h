@@ -144,6 +144,32 @@ constexpr int kDbgSpread = 1;
 #endif
 #endif
 
+// Exit marks (a plain flavour of the counters above, for the test-only library alone:
+// -DKP_EXIT_MARKS, no KP_STAMPS build): webster_par / webster_tail OR one bit per route
+// taken into sc.dbg[0] when the caller set sc.dbg, so a unit test can tell which exit
+// produced t* and which tie route followed. Undefined (libkp.so, libkp_cpusim.so) a
+// mark expands to nothing, statement and semicolon included.
+#if defined(KP_EXIT_MARKS)
+enum WebExit : unsigned long long {
+  WX_REG = 1ull << 0,           // webster_reg hand-off (one-wave block)
+  WX_DROP = 1ull << 1,          // quota adjustment, priorities dropped (C >= N)
+  WX_ADD = 1ull << 2,           // quota adjustment, priorities added (C < N)
+  WX_FIRST = 1ull << 3,         // first-seat rank select
+  WX_BRACKET = 1ull << 4,       // bracket / bisection met without enumeration
+  WX_ENUM = 1ull << 5,          // enumeration and rank_select
+  WX_TIE_ALL = 1ull << 8,       // webster_tail: M >= T
+  WX_TIE_RANK = 1ull << 9,      // webster_tail: rank_select over the tie keys
+  WX_TIE_BISECT = 1ull << 10,   // webster_tail: bisection over tie_key
+  WX_COMPACT_FIRST = 1ull << 12,  // party list filled on the first attempt
+  WX_COMPACT_RETRY = 1ull << 13,  // ... on the retry after kth_largest_vote
+  WX_RETRY_FULL = 1ull << 14,     // the retry overflowed too: no party list
+};
+#define KP_EXIT(B_, sc_, bits_) \
+  if ((sc_).dbg && (B_).tid() == 0) (sc_).dbg[0] |= (unsigned long long)(bits_);
+#else
+#define KP_EXIT(B_, sc_, bits_)
+#endif
+
 struct SerialOut {
   int status = 0;
   int err = 0;
@@ -818,8 +844,10 @@ KP_FI WebRes webster_tail(const BLK& B, WebRes r, Parties parties, double tstar,
   const int64_t M = (int64_t)N - S;
   KP_STAMPD(sc.dbg, 68);
   if (M >= T) {
+    KP_EXIT(B, sc, WX_TIE_ALL)
     r.tie = ~0ull;
   } else if (T <= (int64_t)ecap) {
+    KP_EXIT(B, sc, WX_TIE_RANK)
     int32_t mine = 0;
     parties([&](uint32_t, int64_t v) {
       int64_t base = w_count_r(v, tstar, rts, (int64_t)N + 1, false);
@@ -834,6 +862,7 @@ KP_FI WebRes webster_tail(const BLK& B, WebRes r, Parties parties, double tstar,
     B.sync();
     r.tie = rank_select(B, sc.buf, n, M, false, (uint64_t*)sc.whist);
   } else {
+    KP_EXIT(B, sc, WX_TIE_BISECT)
     uint64_t tlo = 0, thi = (uint64_t)1 << 62;  // smallest x with count(tk <= x) >= M
     while (tlo < thi) {
       uint64_t mid = tlo + (thi - tlo) / 2;
@@ -923,6 +952,7 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
     B.sync();
     np = (int32_t)*ctr;
     if (np <= pcap) {
+      KP_EXIT(B, sc, attempt == 0 ? WX_COMPACT_FIRST : WX_COMPACT_RETRY)
       compact = true;
       break;
     }
@@ -932,6 +962,7 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
       if (B.tid() == 0) *ctr = 0;
       B.sync();
     } else {
+      KP_EXIT(B, sc, attempt == 1 ? WX_RETRY_FULL : 0)
       break;
     }
   }
@@ -966,6 +997,7 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
     bool ok = false;
     WebRes w = webster_reg(B, party, (uint32_t)(e >> 32), (int64_t)(uint32_t)e, N, desc, V, &ok);
     if (ok) {
+      KP_EXIT(B, sc, WX_REG)
       KP_COUNT(sc, 80, 1);
       w.compact = true;
       w.np = np;
@@ -986,6 +1018,7 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
     const int64_t steps = C >= (int64_t)N ? C - (int64_t)N : (int64_t)N - C;
     if (steps <= kAdjMax) {
       const bool drop = C >= (int64_t)N;
+      KP_EXIT(B, sc, drop ? WX_DROP : WX_ADD)
       double tstar = 0;
       for (int64_t left = steps;; left--) {
         // this thread's best held (drop: smallest) or next (add: largest) priority
@@ -1040,6 +1073,7 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
     B.sync();
     KP_STAMPD(sc.dbg, 77);
     if (vmax < 3 * vN) {
+      KP_EXIT(B, sc, WX_FIRST)
       KP_COUNT(sc, 79, 1);
       return webster_tail(B, r, parties, (double)vN, N, desc, sc, ecap, compact, np, Lb, pl);
     }
@@ -1102,8 +1136,10 @@ KP_FI WebRes webster_par(const BLK& B, Parties all_parties, int32_t N, bool desc
   KP_STAMPD(sc.dbg, 66);
   double tstar;
   if (hi - lo <= 1) {
+    KP_EXIT(B, sc, WX_BRACKET)
     tstar = bitsd(lo);
   } else {
+    KP_EXIT(B, sc, WX_ENUM)
     // enumerate the <= 64 priorities in [lo, hi); t* is the (N - chi)-th largest
     const double tl = bitsd(lo), th = bitsd(hi);
     const double rl = 1.0 / tl, rh = 1.0 / th;  // (w_count_r: the same counts, no division per party)

@@ -72,9 +72,10 @@ def test_webster_par_matches_reference_heap(seed):
         N = rng.choice([1, 2, 5, 17, 100, 999, 4000, 65536])
         desc = rng.random() < 0.5
         want = oracle_webster(votes, N, desc)
-        # 0: bisection only; 4: no party compaction; 256: compaction that
-        # overflows on crowded votes (exact N-th largest, retry); 4096: compaction
-        for ecap in (0, 4, 64, 256, 4096):
+        # 0: bisection only; 4: no party compaction; 128 / 160: the capacities the kernels
+        # carve (kOrderEcap, KP_TOP_ECAP); 256: compaction that overflows on crowded votes
+        # (exact N-th largest, retry); 4096: compaction
+        for ecap in (0, 4, 64, 128, 160, 256, 4096):
             got = sim_webster(votes, N, desc, ecap)
             assert got == want, (votes[:20], N, desc, ecap)
 

@@ -7,6 +7,7 @@ import pytest
 
 from karmada_amd import api, synth
 from karmada_amd.engine import Batch, EngineError, Snapshot
+import oracle_lib as O
 
 
 def run(engine, config, n_clusters, n_bind):
@@ -15,6 +16,13 @@ def run(engine, config, n_clusters, n_bind):
     b1 = Batch(snap, structs=u.binding_slice(0, n_bind))
     b2 = Batch(snap, structs=u.binding_slice(n_bind, 2 * n_bind))
     want1, want2 = b1.schedule(), b2.schedule()
+    # ... and kp_schedule_batch's results are the oracle's, slice by slice
+    for lo, want in ((0, want1), (n_bind, want2)):
+        ba, n = u.binding_slice(lo, lo + n_bind)
+        ref = O.schedule_c(u.clusters, u.n_clusters, ba, n, api.options(), O.FAST, 8)
+        bad = [i for i in range(n) if want[i] != ref[i]]
+        assert not bad, (f"config {config}: {len(bad)}/{n} bindings of slice {lo} differ from the oracle; first "
+                         f"{bad[0]}: engine={want[bad[0]]} oracle={ref[bad[0]]}")
 
     def py(r):
         return api.results_to_python(r.status, r.err_code, r.err_arg, r.offsets, r.cluster_idx, r.replicas,
